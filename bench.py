@@ -19,6 +19,12 @@ vs_baseline divides that measured speedup by the reference's default 3.0x
 operator score — the reference repo publishes no absolute
 wall-clock numbers in-tree.
 
+A plain run stages the data, warms up, times the K steps and prints the
+result line; the CPU-backend baseline (and with it speedup_vs_cpu_backend /
+vs_baseline) is measured only under --full. --dump-outputs DIR writes the
+result columns of the last timed step as DIR/<query>.<NN>_<column>.npy
+plus a .kind.npy marking NULL / non-finite rows; every value is finite.
+
 Timing: barrier + torch.cuda.synchronize on both sides, MAX over ranks.
 """
 from __future__ import annotations
@@ -88,6 +94,59 @@ def _cpu_baseline(data_dir: str, procs: int, steps: int) -> float:
     return (time.perf_counter() - t0) / steps
 
 
+_KIND_VALUE, _KIND_NULL, _KIND_NAN, _KIND_POS_INF, _KIND_NEG_INF = range(5)
+
+
+def _column_arrays(values):
+    """One collected result column as two float64 arrays, both finite
+    everywhere: (data, kind). data holds numerics and decimals by value and
+    strings by the CRC-32 of their UTF-8 bytes (exact in float64, so two
+    runs compare string columns for equality); kind is 0 for such a value
+    and 1 / 2 / 3 / 4 for NULL / NaN / +inf / -inf, where data is 0."""
+    import math
+    import zlib
+
+    import numpy as np
+
+    data = np.zeros(len(values), dtype=np.float64)
+    kind = np.zeros(len(values), dtype=np.float64)
+    for i, v in enumerate(values):
+        if v is None:
+            kind[i] = _KIND_NULL
+        elif isinstance(v, str):
+            data[i] = float(zlib.crc32(v.encode("utf-8")))
+        else:
+            x = float(v)
+            if math.isnan(x):
+                kind[i] = _KIND_NAN
+            elif math.isinf(x):
+                kind[i] = _KIND_POS_INF if x > 0 else _KIND_NEG_INF
+            else:
+                data[i] = x
+    return data, kind
+
+
+def _dump_outputs(out_dir: str, tables, results, suffix: str = "") -> None:
+    """Write what the last timed run_power() returned: per query result
+    column one float64 <name>.npy with the values and one <name>.kind.npy
+    marking NULL / non-finite rows (every query ends in a LIMIT, a few KB
+    in all)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    plans = dict(POWER_RUN)
+    for qname, rows in results:
+        fields = plans[qname](tables).schema.fields
+        cols = list(zip(*rows)) if rows else [()] * len(fields)
+        for j, (f, values) in enumerate(zip(fields, cols)):
+            safe = "".join(c if c.isalnum() or c == "_" else "_"
+                           for c in f.name)
+            base = os.path.join(out_dir, f"{qname}.{j:02d}_{safe}{suffix}")
+            data, kind = _column_arrays(values)
+            np.save(base + ".npy", data)
+            np.save(base + ".kind.npy", kind)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -104,8 +163,16 @@ def main():
                     help="comma list to restrict the suite (debug)")
     ap.add_argument("--per-query", action="store_true",
                     help="print per-query wall times to stderr (untimed)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the CPU-backend baseline (speedup / "
+                         "vs_baseline); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's query results as "
+                         "DIR/<query>.<NN>_<column>.npy (float64) with a "
+                         ".kind.npy marking NULL / non-finite rows")
     ap.add_argument("--cpu-baseline-steps", type=int, default=1,
-                    help="0 disables the CPU-backend baseline measurement")
+                    help="with --full: steps of the CPU-backend baseline "
+                         "(0 disables it)")
     ap.add_argument("--cpu-baseline-procs", type=int,
                     default=min(16, os.cpu_count() or 1))
     args = ap.parse_args()
@@ -178,9 +245,10 @@ def main():
     gc.collect()
     gc.freeze()
     gc.disable()
+    last = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        run_power(tables, queries)
+        last = run_power(tables, queries)
     barrier_sync()
     elapsed = time.perf_counter() - t0
     gc.enable()
@@ -198,8 +266,12 @@ def main():
     rows_per_step = args.rows_per_gpu * n_queries * n_gpus
     value = rows_per_step * args.steps / elapsed
 
+    if args.dump_outputs and last is not None:
+        _dump_outputs(args.dump_outputs, tables, last,
+                      suffix=f".rank{rank}" if distributed else "")
+
     speedup = None
-    if rank == 0 and args.cpu_baseline_steps > 0:
+    if rank == 0 and args.full and args.cpu_baseline_steps > 0:
         tcpu = _cpu_baseline(data_dir, args.cpu_baseline_procs,
                              args.cpu_baseline_steps)
         speedup = tcpu / (elapsed / args.steps)

@@ -227,12 +227,21 @@ def stage(data_dir: str, rows: int, rank: int, world: int,
     stamp = os.path.join(data_dir, f".staged-r{rank}-{rows}x{world}")
     if force or not os.path.exists(stamp):
         per = rows // partitions
-        for p in range(partitions):
+
+        def write_partition(p: int) -> None:
             n = per if p < partitions - 1 else rows - per * (partitions - 1)
             t = gen_store_sales_partition(n, seed=(rank + 1) * 1000 + p)
             pq.write_table(
                 t, os.path.join(fact_dir, f"part-{rank:03d}-{p:03d}.parquet"),
                 **_FACT_OPTS)
+
+        # partitions are independently seeded, so generating them on a few
+        # threads writes the same files (numpy's generators and the parquet
+        # writer release the GIL); 4 bounds the transient host memory
+        from concurrent.futures import ThreadPoolExecutor
+
+        with ThreadPoolExecutor(min(4, partitions)) as pool:
+            list(pool.map(write_partition, range(partitions)))
         if rank == 0:
             for name, gen in (("date_dim", gen_date_dim),
                               ("item", gen_item), ("store", gen_store),

@@ -459,9 +459,10 @@ class TestPinnedHostPool:
             host_pool.configure(None)
 
 
-def test_task_metrics_accumulators():
+def test_task_metrics_accumulators(tmp_path, monkeypatch):
     """GpuTaskMetrics analogue: spill bytes/time, retry counts and
     semaphore wait surface through sr.task_metrics()."""
+    monkeypatch.setenv("RAPIDS_SPILL_PATH", str(tmp_path))
     import numpy as np
 
     import spark_rapids_amd as sr
