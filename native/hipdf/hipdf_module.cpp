@@ -530,12 +530,16 @@ PYBIND11_MODULE(hipdf, m) {
   m.def("host_unregister", [](int64_t ptr) {
     hipHostUnregister((void*)ptr);
   });
+  // GIL released: from pageable memory (the parquet file mapping) this
+  // returns only after the runtime has staged the whole source, and the
+  // reader's prefetch threads and the kernel-launching thread must not
+  // queue behind one another for that long
   m.def("memcpy_h2d", [](int64_t dst, int64_t src, int64_t nbytes,
                          int64_t stream) -> int {
     return (int)hipMemcpyAsync((void*)dst, (const void*)src,
                                (size_t)nbytes, hipMemcpyHostToDevice,
                                S(stream));
-  });
+  }, py::call_guard<py::gil_scoped_release>());
   m.def("rle_walk_host",
         [](int64_t data, int64_t nbytes, int bw, int64_t n_values,
            int64_t src_base, int64_t out_base, int64_t runs,

@@ -42,11 +42,9 @@ _PHYS_NP = {
 }
 
 
-_PINNED = __import__("threading").local()
-
-# (path, mtime) -> (mmap, base_addr, nbytes, registered) — the mapping is
-# hipHostRegister'ed once so chunk uploads are direct DMA from the page
-# cache (no pinned bounce memcpy); kept alive for the process lifetime
+# (path, mtime) -> (mmap, memoryview, base_addr, nbytes, registered) — the
+# mapping is never hipHostRegister'ed (see the NOTE in _file_mmap); kept
+# alive for the process lifetime
 _MMAP_CACHE: dict = {}
 _MMAP_LOCK = __import__("threading").Lock()
 
@@ -67,8 +65,8 @@ def _file_mmap(path: str):
         base = arr.ctypes.data
         # NOTE: hipHostRegister on the file-backed mapping looked
         # attractive (direct DMA from page cache) but the GPU faults on
-        # DMA from MAP_PRIVATE file pages on this stack — uploads bounce
-        # through the per-thread pinned buffer instead
+        # DMA from MAP_PRIVATE file pages on this stack — uploads are
+        # pageable copies staged by the runtime instead (_upload_parts)
         if len(_MMAP_CACHE) > 512:
             _MMAP_CACHE.clear()
         hit = (mm, memoryview(mm), base, arr.nbytes, False)
@@ -78,16 +76,24 @@ def _file_mmap(path: str):
 
 def _upload_parts(parts, ext, stream, torch_dtype=torch.uint8,
                   pad: int = 0) -> torch.Tensor:
-    """Upload several host byte views into one device buffer. Views that
-    live inside a hipHostRegister'ed mapping go straight to DMA
-    (hipMemcpyAsync from pinned memory); others bounce through the
-    per-thread pinned buffer."""
+    """Upload several host byte views back to back into one device
+    buffer on `stream`. The views are pageable memory (slices of the file
+    mapping, numpy temporaries), so each hipMemcpyAsync returns once the
+    runtime has staged its source: the views may be reused or unmapped as
+    soon as this returns. ext.memcpy_h2d releases the GIL for that time,
+    so the prefetch threads copy in parallel."""
+    import time as _t
+
+    from .parquet import PHASE_STATS
+
     arrs = [a if isinstance(a, np.ndarray) else
             np.frombuffer(a, dtype=np.uint8) for a in parts]
-    total = sum(a.nbytes for a in arrs) + pad
+    nbytes = sum(a.nbytes for a in arrs)
+    total = nbytes + pad
     if total == 0:
         return torch.zeros(0, dtype=torch_dtype, device="cuda")
     dev = torch.empty(total, dtype=torch.uint8, device="cuda")
+    t0 = _t.perf_counter()
     off = 0
     for a in arrs:
         n = a.nbytes
@@ -97,45 +103,20 @@ def _upload_parts(parts, ext, stream, torch_dtype=torch.uint8,
         if rc != 0:
             raise RuntimeError(f"hipMemcpyAsync failed rc={rc}")
         off += n
+    PHASE_STATS["upload_s"] += _t.perf_counter() - t0
+    PHASE_STATS["upload_bytes"] += nbytes
     if pad:
         dev[total - pad:] = 0
     itemsize = torch.empty(0, dtype=torch_dtype).element_size()
-    return dev.view(torch_dtype) if itemsize == 1 else         dev[: (total // itemsize) * itemsize].view(torch_dtype)
-
-
-def _upload(data, torch_dtype=torch.uint8) -> torch.Tensor:
-    """bytes/ndarray -> device tensor through a reusable pinned staging
-    buffer (one host memcpy + async DMA, instead of frombuffer().copy()
-    + a pageable H2D which stages internally anyway). Per-thread buffer:
-    the multi-file prefetch pool uploads concurrently."""
-    if isinstance(data, np.ndarray):
-        arr = data.view(np.uint8).reshape(-1)
-    else:
-        arr = np.frombuffer(data, dtype=np.uint8)
-    nbytes = arr.nbytes
-    if nbytes == 0:
-        return torch.zeros(0, dtype=torch_dtype, device="cuda")
-    buf = getattr(_PINNED, "buf", None)
-    if buf is None or buf.numel() < nbytes:
-        cap = max(nbytes, 1 << 20)
-        cap = 1 << (cap - 1).bit_length()
-        buf = torch.empty(cap, dtype=torch.uint8, pin_memory=True)
-        _PINNED.buf = buf
-    import time as _t
-
-    from .parquet import PHASE_STATS
-
-    t0 = _t.perf_counter()
-    buf.numpy()[:nbytes] = arr
-    dev = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
-    # blocking copy: the pinned buffer is reused by the next upload on
-    # this thread, so the DMA must complete before returning
-    dev.copy_(buf[:nbytes])
-    PHASE_STATS["upload_s"] += _t.perf_counter() - t0
-    PHASE_STATS["upload_bytes"] += nbytes
-    itemsize = torch.empty(0, dtype=torch_dtype).element_size()
     return dev.view(torch_dtype) if itemsize == 1 else \
-        dev[: (nbytes // itemsize) * itemsize].view(torch_dtype)
+        dev[: (total // itemsize) * itemsize].view(torch_dtype)
+
+
+def _upload_array(arr: np.ndarray, ext, stream) -> torch.Tensor:
+    """One contiguous numpy array -> device tensor of the same dtype."""
+    flat = np.ascontiguousarray(arr).reshape(-1)
+    return _upload_parts([flat.view(np.uint8)], ext, stream,
+                         torch.from_numpy(flat[:0]).dtype)
 
 
 def _codec(name: str):
@@ -630,16 +611,16 @@ class _ChunkDecoder:
         offs_h[0] = 0
         np.cumsum(lens_h, out=offs_h[1:])
         page = _upload_parts([arr], self.ext, self.s)
-        starts = torch.from_numpy(starts_h).cuda()
-        lens = torch.from_numpy(lens_h).cuda()
-        scanned = torch.from_numpy(offs_h[:-1]).cuda()
+        starts = _upload_array(starts_h, self.ext, self.s)
+        lens = _upload_array(lens_h, self.ext, self.s)
+        scanned = _upload_array(offs_h[:-1], self.ext, self.s)
         out_bytes = torch.empty(max(total, 1), dtype=torch.uint8,
                                 device="cuda")[:total]
         if total:
             self.ext.substr_copy(page.data_ptr(), starts.data_ptr(),
                                  lens.data_ptr(), scanned.data_ptr(),
                                  out_bytes.data_ptr(), count, self.s)
-        offs = torch.from_numpy(offs_h.astype(np.int32)).cuda()
+        offs = _upload_array(offs_h.astype(np.int32), self.ext, self.s)
         return offs, out_bytes
 
     # -- data pages ------------------------------------------------------
