@@ -87,6 +87,15 @@ void hipdf_join_count(int, const void*, const void*, const void*, int,
 void hipdf_join_fill(int, const void*, const void*, const void*, int,
                      const void*, const void*, int64_t, const void*, void*,
                      void*, void*, int64_t, hipStream_t);
+int64_t join_probe_num_blocks(int64_t);
+void hipdf_join_check_unique(const void*, int, const void*, void*, int64_t,
+                             hipStream_t);
+void hipdf_join_probe_unique(int, int, const void*, const void*, const void*,
+                             const void*, const void*, const void*, int,
+                             const void*, const void*, int64_t, void*, void*,
+                             void*, int64_t, hipStream_t);
+void hipdf_join_compact_unique(int, const void*, const void*, void*, void*,
+                               int64_t, hipStream_t);
 int64_t part_num_blocks(int64_t);
 int64_t sort_num_blocks(int64_t);
 void hipdf_dec64_mul_div(int, const void*, const void*, const void*,
@@ -808,6 +817,33 @@ PYBIND11_MODULE(hipdf, m) {
     hipdf_join_fill(how, P(lh), P(lk), P(rk), nkeys, P(head), P(next), cap,
                     P(offsets), PM(lmap), PM(rmap), PM(right_matched), n,
                     S(stream));
+    check_async();
+  });
+  m.def("join_probe_num_blocks", &join_probe_num_blocks);
+  m.def("join_check_unique", [](int64_t keys, int nkeys, int64_t next,
+                                int64_t dup_flag, int64_t n, int64_t stream) {
+    hipdf_join_check_unique(P(keys), nkeys, P(next), PM(dup_flag), n,
+                            S(stream));
+    check_async();
+  });
+  m.def("join_probe_unique", [](int how, int key_type, int64_t lkey,
+                                int64_t lvalid, int64_t rkey, int64_t lh,
+                                int64_t lk, int64_t rk, int nkeys,
+                                int64_t head, int64_t next, int64_t cap,
+                                int64_t match, int64_t right_matched,
+                                int64_t block_counts, int64_t n,
+                                int64_t stream) {
+    hipdf_join_probe_unique(how, key_type, P(lkey), P(lvalid), P(rkey), P(lh),
+                            P(lk), P(rk), nkeys, P(head), P(next), cap,
+                            PM(match), PM(right_matched), PM(block_counts), n,
+                            S(stream));
+    check_async();
+  });
+  m.def("join_compact_unique", [](int how, int64_t match, int64_t offsets,
+                                  int64_t lmap, int64_t rmap, int64_t n,
+                                  int64_t stream) {
+    hipdf_join_compact_unique(how, P(match), P(offsets), PM(lmap), PM(rmap),
+                              n, S(stream));
     check_async();
   });
 

@@ -4,37 +4,7 @@
 // Murmur3Hash so GPU shuffle partitioning lines up with CPU Spark
 // (reference analogue: spark-rapids-jni Hash.murmurHash32 — SURVEY.md §2.8B).
 #include "hipdf_common.h"
-
-__device__ __forceinline__ uint32_t rotl32(uint32_t x, int r) {
-  return (x << r) | (x >> (32 - r));
-}
-__device__ __forceinline__ uint32_t mix_k1(uint32_t k1) {
-  k1 *= 0xCC9E2D51u;
-  k1 = rotl32(k1, 15);
-  return k1 * 0x1B873593u;
-}
-__device__ __forceinline__ uint32_t mix_h1(uint32_t h1, uint32_t k1) {
-  h1 ^= k1;
-  h1 = rotl32(h1, 13);
-  return h1 * 5u + 0xE6546B64u;
-}
-__device__ __forceinline__ uint32_t fmix(uint32_t h1, uint32_t len) {
-  h1 ^= len;
-  h1 ^= h1 >> 16;
-  h1 *= 0x85EBCA6Bu;
-  h1 ^= h1 >> 13;
-  h1 *= 0xC2B2AE35u;
-  h1 ^= h1 >> 16;
-  return h1;
-}
-__device__ __forceinline__ uint32_t hash_int(uint32_t v, uint32_t seed) {
-  return fmix(mix_h1(seed, mix_k1(v)), 4);
-}
-__device__ __forceinline__ uint32_t hash_long(uint64_t v, uint32_t seed) {
-  uint32_t h1 = mix_h1(seed, mix_k1((uint32_t)v));
-  h1 = mix_h1(h1, mix_k1((uint32_t)(v >> 32)));
-  return fmix(h1, 8);
-}
+#include "murmur3.h"
 
 // hash kinds: how the column's value maps into murmur input
 enum HashKind : int {

@@ -195,6 +195,23 @@ def join_gather_maps(left: ColumnBatch, right: ColumnBatch,
         left, right, list(left_keys), list(right_keys), how, right_matched)
 
 
+def join_build_table(right: ColumnBatch, right_keys: Sequence[int]):
+    """Build the join table over the build side once; probe it with
+    join_probe for every left batch. The table belongs to the backend that
+    built it (device build side -> device probes)."""
+    return backend_for(*right.columns).join_build_table(
+        right, list(right_keys))
+
+
+def join_probe(table, left: ColumnBatch, left_keys: Sequence[int], how: str,
+               right_matched=None) -> Tuple[Column, Optional[Column]]:
+    """Gather maps of `left` against a table from join_build_table; same
+    return contract as join_gather_maps."""
+    backend = cpu_backend if isinstance(table, tuple) else _gpu_backend()
+    return backend.join_probe(table, left, list(left_keys), how,
+                              right_matched)
+
+
 def concat_batches(batches: Sequence[ColumnBatch]) -> ColumnBatch:
     assert batches
     return backend_for(*batches[0].columns).concat_batches(list(batches))

@@ -1256,6 +1256,19 @@ def join_gather_maps(left: ColumnBatch, right: ColumnBatch,
     raise NotImplementedError(f"cpu join {how}")
 
 
+def join_build_table(right: ColumnBatch, right_keys: List[int]):
+    """Build/probe split of join_gather_maps; the host join has no table to
+    keep, so the 'table' is the build batch and its key indices."""
+    return (right, list(right_keys))
+
+
+def join_probe(table, left: ColumnBatch, left_keys: List[int], how: str,
+               right_matched=None):
+    right, right_keys = table
+    return join_gather_maps(left, right, left_keys, right_keys, how,
+                            right_matched)
+
+
 def _key_series(col: Column):
     import pandas as pd
 

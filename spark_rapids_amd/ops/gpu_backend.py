@@ -1856,39 +1856,152 @@ def _gb_collect(vc: Column, row_gid: torch.Tensor, selp, n: int,
 # join
 # ---------------------------------------------------------------------------
 
-def join_gather_maps(left: ColumnBatch, right: ColumnBatch,
-                     left_keys: List[int], right_keys: List[int], how: str,
-                     right_matched: Optional[torch.Tensor] = None):
+_JOIN_SEED = 42  # JOIN_SEED in native/hipdf/kernels/join.hip
+
+
+class JoinTable:
+    """Chained hash table over the build side of an equi-join, built once
+    and probed by every left batch. `unique` says no two non-null build rows
+    share a key, which lets the probe take the single-pass path."""
+
+    __slots__ = ("keys", "desc", "hashes", "head", "next", "cap", "num_rows",
+                 "unique")
+
+    def __init__(self, keys, desc, hashes, head, nxt, cap, num_rows, unique):
+        self.keys = keys          # build key columns (keeps buffers alive)
+        self.desc = desc          # device KeyCol descriptors of the keys
+        self.hashes = hashes      # murmur3 row hashes of the build keys
+        self.head = head
+        self.next = nxt
+        self.cap = cap
+        self.num_rows = num_rows
+        self.unique = unique
+
+
+def join_build_table(right: ColumnBatch, right_keys: List[int]) -> JoinTable:
     s = _stream()
-    nl, nr = left.num_rows, right.num_rows
-    lk = [left.columns[i] for i in left_keys]
+    nr = right.num_rows
     rk = [right.columns[i] for i in right_keys]
     cap = max(1024, _next_pow2(2 * max(nr, 1)))
-    rh = _murmur3_tensor(rk, 42)
+    rh = _murmur3_tensor(rk, _JOIN_SEED)
     rdesc = _key_desc(rk)
-    ldesc = _key_desc(lk)
     head = torch.full((cap,), -1, dtype=torch.int32, device="cuda")
     nxt = torch.empty(max(nr, 1), dtype=torch.int32, device="cuda")
     ext.join_build(rh.data_ptr(), rdesc.data_ptr(), len(rk), head.data_ptr(),
                    nxt.data_ptr(), cap, nr, s)
-    lh = _murmur3_tensor(lk, 42)
-    counts = torch.empty(nl, dtype=torch.int64, device="cuda")
-    ext.join_count(_JOIN[how], lh.data_ptr(), ldesc.data_ptr(),
-                   rdesc.data_ptr(), len(lk), head.data_ptr(), nxt.data_ptr(),
-                   cap, counts.data_ptr(), nl, s)
+    unique = True
+    if nr > 1:
+        dup = torch.zeros(1, dtype=torch.int32, device="cuda")
+        ext.join_check_unique(rdesc.data_ptr(), len(rk), nxt.data_ptr(),
+                              dup.data_ptr(), nr, s)
+        unique = int(dup.item()) == 0
+    return JoinTable(rk, rdesc, rh, head, nxt, cap, nr, unique)
+
+
+def _join_inline_key_type(lk: List[Column], rk: List[Column]) -> int:
+    """HType of the key when the probe can hash it inline (one integer key
+    column of the same type on both sides), else -1."""
+    if len(lk) != 1 or lk[0].dtype.id is not rk[0].dtype.id:
+        return -1
+    if _HASH_KIND.get(lk[0].dtype.id) not in (_HK_INT, _HK_LONG):
+        return -1
+    return _ht(lk[0].dtype)
+
+
+_ARANGE_I32: dict = {}  # device index -> cached int32 arange
+
+
+def _identity_map(n: int) -> torch.Tensor:
+    """Read-only view of a cached int32 arange (the left map of a left/full
+    join against a unique build side). Callers only gather through it."""
+    dev = torch.cuda.current_device()
+    cached = _ARANGE_I32.get(dev)
+    if cached is None or cached.numel() < n:
+        cached = torch.arange(max(n, 1 << 20), dtype=torch.int32,
+                              device="cuda")
+        # the cache outlives the stream that filled it
+        torch.cuda.current_stream().synchronize()
+        _ARANGE_I32[dev] = cached
+    return cached[:n]
+
+
+def _join_probe_unique(table: JoinTable, lk: List[Column], nl: int, how: str,
+                       right_matched: Optional[torch.Tensor]):
+    """Single-pass probe: every left row has 0 or 1 matches."""
+    s = _stream()
+    rk = table.keys
+    key_type = _join_inline_key_type(lk, rk)
+    if key_type >= 0:
+        lkey, lvalid, rkey = (lk[0].data.data_ptr(), _ptr(lk[0].validity),
+                              rk[0].data.data_ptr())
+        lh = ldesc = None
+    else:
+        lkey = lvalid = rkey = 0
+        lh = _murmur3_tensor(lk, _JOIN_SEED)
+        ldesc = _key_desc(lk)
+    match = torch.empty(max(nl, 1), dtype=torch.int32, device="cuda")[:nl]
+    every_row = how in ("left", "full")
+    counts = None if every_row else torch.empty(
+        ext.join_probe_num_blocks(nl), dtype=torch.int64, device="cuda")
+    ext.join_probe_unique(_JOIN[how], key_type, lkey, lvalid, rkey, _ptr(lh),
+                          _ptr(ldesc), table.desc.data_ptr(), len(lk),
+                          table.head.data_ptr(), table.next.data_ptr(),
+                          table.cap, match.data_ptr(), _ptr(right_matched),
+                          _ptr(counts), nl, s)
+    if every_row:
+        # one output row per probe row: rmap is match, lmap the identity
+        return _identity_map(nl), match, nl
     offsets, total = _exclusive_scan_i64(counts)
     lmap = torch.empty(max(total, 1), dtype=torch.int32, device="cuda")[:total]
     rmap = torch.empty(max(total, 1), dtype=torch.int32, device="cuda")[:total] \
-        if how in ("inner", "left", "full") else None
+        if how == "inner" else None
     if total:
-        ext.join_fill(_JOIN[how], lh.data_ptr(), ldesc.data_ptr(),
-                      rdesc.data_ptr(), len(lk), head.data_ptr(),
-                      nxt.data_ptr(), cap, offsets.data_ptr(),
-                      lmap.data_ptr(), _ptr(rmap), _ptr(right_matched), nl, s)
+        ext.join_compact_unique(_JOIN[how], match.data_ptr(),
+                                offsets.data_ptr(), lmap.data_ptr(),
+                                _ptr(rmap), nl, s)
+    return lmap, rmap, total
+
+
+def join_probe(table: JoinTable, left: ColumnBatch, left_keys: List[int],
+               how: str, right_matched: Optional[torch.Tensor] = None):
+    s = _stream()
+    nl = left.num_rows
+    lk = [left.columns[i] for i in left_keys]
+    if table.unique and nl:
+        lmap, rmap, total = _join_probe_unique(table, lk, nl, how,
+                                               right_matched)
+    else:
+        # general many-to-many path: count, scan, fill
+        ldesc = _key_desc(lk)
+        rdesc, head, nxt, cap = table.desc, table.head, table.next, table.cap
+        lh = _murmur3_tensor(lk, _JOIN_SEED)
+        counts = torch.empty(nl, dtype=torch.int64, device="cuda")
+        ext.join_count(_JOIN[how], lh.data_ptr(), ldesc.data_ptr(),
+                       rdesc.data_ptr(), len(lk), head.data_ptr(),
+                       nxt.data_ptr(), cap, counts.data_ptr(), nl, s)
+        offsets, total = _exclusive_scan_i64(counts)
+        lmap = torch.empty(max(total, 1), dtype=torch.int32,
+                           device="cuda")[:total]
+        rmap = torch.empty(max(total, 1), dtype=torch.int32,
+                           device="cuda")[:total] \
+            if how in ("inner", "left", "full") else None
+        if total:
+            ext.join_fill(_JOIN[how], lh.data_ptr(), ldesc.data_ptr(),
+                          rdesc.data_ptr(), len(lk), head.data_ptr(),
+                          nxt.data_ptr(), cap, offsets.data_ptr(),
+                          lmap.data_ptr(), _ptr(rmap), _ptr(right_matched),
+                          nl, s)
     lcol = Column(DType.int32(), total, lmap, None, null_count=0)
     rcol = Column(DType.int32(), total, rmap, None, null_count=0) \
         if rmap is not None else None
     return lcol, rcol
+
+
+def join_gather_maps(left: ColumnBatch, right: ColumnBatch,
+                     left_keys: List[int], right_keys: List[int], how: str,
+                     right_matched: Optional[torch.Tensor] = None):
+    return join_probe(join_build_table(right, right_keys), left, left_keys,
+                      how, right_matched)
 
 
 # ---------------------------------------------------------------------------

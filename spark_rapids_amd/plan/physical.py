@@ -583,6 +583,11 @@ class HashJoinExec(PhysicalExec):
             yield from self._execute_subpartitioned(
                 rtable, lsource, lkidx, rkidx, left.schema)
             return
+        # the build side is the same for every left batch: one hash table
+        # (and one uniqueness check) per join, probed batch by batch
+        jtable = None
+        if rtable is not None and rtable.num_rows and self.condition is None:
+            jtable = ops.join_build_table(rtable, rkidx)
         for lbatch in lsource:
             if lbatch.num_rows == 0:
                 continue
@@ -597,8 +602,8 @@ class HashJoinExec(PhysicalExec):
                 yield from self._emit_conditional(lbatch, rtable, lkidx,
                                                   rkidx, right_matched)
                 continue
-            lmap, rmap = ops.join_gather_maps(lbatch, rtable, lkidx, rkidx,
-                                              self.how, right_matched)
+            lmap, rmap = ops.join_probe(jtable, lbatch, lkidx, self.how,
+                                        right_matched)
             if self.how in ("semi", "anti"):
                 out = ops.gather(lbatch, lmap, negatives=False)
                 if out.num_rows:
