@@ -36,6 +36,7 @@ KERNELS = [
     "kernels/regex.hip",
     "kernels/cast_str.hip",
     "kernels/datetime.hip",
+    "kernels/lists.hip",
     "pool.hip",
 ]
 

@@ -240,6 +240,23 @@ void hipdf_str_locate(const void*, const void*, const void*, int32_t,
                       int32_t, void*, int64_t, hipStream_t);
 }
 
+// lists: segmented sort / distinct / arg-min-max inside LIST rows
+extern "C" {
+int hipdf_list_block_cap();
+void hipdf_list_sort_wave(int, const void*, const void*, const void*,
+                          const void*, int, int, int, void*, int64_t,
+                          hipStream_t);
+void hipdf_list_sort_block(int, const void*, const void*, const void*,
+                           const void*, const void*, int64_t, int, int,
+                           void*, hipStream_t);
+void hipdf_list_distinct_flags(int, const void*, const void*, const void*,
+                               const void*, int64_t, const void*, void*,
+                               int64_t, hipStream_t);
+void hipdf_list_argminmax(int, const void*, const void*, const void*,
+                          const void*, const void*, int, int, void*, int64_t,
+                          hipStream_t);
+}
+
 extern "C" {
 void hipdf_tz_convert(const void*, const void*, const void*, int, int,
                       void*, int64_t, hipStream_t);
@@ -1232,6 +1249,40 @@ PYBIND11_MODULE(hipdf, m) {
   m.def("part_scatter", [](int64_t part, int nparts, int64_t offsets,
                            int64_t perm, int64_t n, int64_t stream) {
     hipdf_part_scatter(P(part), nparts, P(offsets), PM(perm), n, S(stream));
+    check_async();
+  });
+  m.def("list_block_cap", &hipdf_list_block_cap);
+  m.def("list_sort_wave", [](int t, int64_t data, int64_t eoffs,
+                             int64_t cvalid, int64_t offsets, int w,
+                             bool nulls_first, bool desc, int64_t perm,
+                             int64_t n, int64_t stream) {
+    hipdf_list_sort_wave(t, P(data), P(eoffs), P(cvalid), P(offsets), w,
+                         nulls_first, desc, PM(perm), n, S(stream));
+    check_async();
+  });
+  m.def("list_sort_block", [](int t, int64_t data, int64_t eoffs,
+                              int64_t cvalid, int64_t offsets, int64_t rows,
+                              int64_t nrows, bool nulls_first, bool desc,
+                              int64_t perm, int64_t stream) {
+    hipdf_list_sort_block(t, P(data), P(eoffs), P(cvalid), P(offsets),
+                          P(rows), nrows, nulls_first, desc, PM(perm),
+                          S(stream));
+    check_async();
+  });
+  m.def("list_distinct_flags", [](int t, int64_t data, int64_t eoffs,
+                                  int64_t cvalid, int64_t offsets, int64_t n,
+                                  int64_t perm, int64_t keep, int64_t total,
+                                  int64_t stream) {
+    hipdf_list_distinct_flags(t, P(data), P(eoffs), P(cvalid), P(offsets), n,
+                              P(perm), PM(keep), total, S(stream));
+    check_async();
+  });
+  m.def("list_argminmax", [](int t, int64_t data, int64_t eoffs,
+                             int64_t cvalid, int64_t offsets, int64_t rvalid,
+                             int w, bool is_max, int64_t out, int64_t n,
+                             int64_t stream) {
+    hipdf_list_argminmax(t, P(data), P(eoffs), P(cvalid), P(offsets),
+                         P(rvalid), w, is_max, PM(out), n, S(stream));
     check_async();
   });
 }

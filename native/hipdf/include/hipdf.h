@@ -96,6 +96,38 @@ void hipdf_gb_agg(int op, int t, const void* vals, const void* vvalid,
                   int acc_is_double, int32_t ngroups, int64_t n,
                   hipStream_t stream);
 
+/* ---- lists: segmented ops inside the rows of a LIST column ------------- */
+/* t: HipdfType of the child, or 7 for a string child (data = bytes,
+ * eoffs = the child's int32 offsets; eoffs is ignored otherwise).
+ * offsets: the LIST's int32[n+1]; offsets[0] need not be 0. cvalid: child
+ * validity words or NULL. perm: int32[offsets[n]-offsets[0]] of GLOBAL child
+ * indices, entry (p - offsets[0]) for child position p. Order inside a list
+ * is (null rank, sort key, original index). */
+int hipdf_list_block_cap(void); /* longest list the block tier sorts */
+/* rows of length <= w (w in 8/16/32/64): w lanes own one list; longer rows
+ * are left untouched */
+void hipdf_list_sort_wave(int t, const void* data, const void* eoffs,
+                          const void* cvalid, const void* offsets, int w,
+                          int nulls_first, int desc, void* perm, int64_t n,
+                          hipStream_t stream);
+/* one block per listed row (int32 rows[nrows], each of length
+ * <= hipdf_list_block_cap()) */
+void hipdf_list_sort_block(int t, const void* data, const void* eoffs,
+                           const void* cvalid, const void* offsets,
+                           const void* rows, int64_t nrows, int nulls_first,
+                           int desc, void* perm, hipStream_t stream);
+/* perm from an ascending sort; keep: uint8[total], 1 = first occurrence */
+void hipdf_list_distinct_flags(int t, const void* data, const void* eoffs,
+                               const void* cvalid, const void* offsets,
+                               int64_t n, const void* perm, void* keep,
+                               int64_t total, hipStream_t stream);
+/* out: int32[n] global child index of the first min (max) non-null element,
+ * -1 for a null (rvalid), empty or all-null list */
+void hipdf_list_argminmax(int t, const void* data, const void* eoffs,
+                          const void* cvalid, const void* offsets,
+                          const void* rvalid, int w, int is_max, void* out,
+                          int64_t n, hipStream_t stream);
+
 /* ---- device memory pool (pool.hip) ------------------------------------ */
 int hipdf_pool_init(double fraction, size_t bytes);
 void* hipdf_pool_alloc(size_t n);

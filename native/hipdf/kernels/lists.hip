@@ -1,0 +1,406 @@
+// Segmented operations inside the rows of a LIST column (reference analogue:
+// GpuSortArray / GpuArraySort / GpuArrayDistinct / GpuArrayMin / GpuArrayMax
+// in collectionOperations.scala, reached there through cudf segmented sort).
+//
+// Inputs are always the LIST offsets (int32[n+1], offsets[0] need not be 0),
+// the child's values and the child's validity bitmask. The sort produces an
+// int32 permutation of GLOBAL child indices, written at position
+// (p - offsets[0]) for child position p, which the caller applies with the
+// ordinary gather (validity and string bytes follow for free).
+//
+// Ordering inside one list is (null rank, key, original index): key is the
+// radix sort's order-preserving transform (sort_keys.h), descending inverts
+// the key but never the index tie-break, so the result is that of a stable
+// sort. Strings use an 8-byte big-endian prefix as the key and compare the
+// remaining bytes on a tie (shorter string first on a common prefix).
+//
+// Tiers by list length:
+//   <= 64    W lanes (8/16/32/64) own one list, one element per lane,
+//            bitonic network over __shfl_xor — no LDS, up to 8 lists/wave
+//   <= 2048  one 256-thread block per list, bitonic in LDS over
+//            (u64 key, u32 rank|local index) = 24 KB at the cap
+//   longer   host routes those rows through the global radix sort
+#include "hipdf_common.h"
+#include "sort_keys.h"
+
+#define LIST_BLOCK 256
+#define LIST_BLOCK_CAP 2048
+#define LT_STR 7        // element type id for strings (after HT_F64)
+#define RANK_PAD 2u     // padding sentinel: sorts after real nulls
+
+// ---- element sources -----------------------------------------------------
+
+template <typename T>
+struct FixedSrc {
+  const T* data;
+  __device__ __forceinline__ uint64_t key(int32_t i) const {
+    return sort_key_of<T>(data[i]);
+  }
+  __device__ __forceinline__ int tie(int32_t, int32_t) const { return 0; }
+};
+
+struct StrSrc {
+  const int32_t* offs;
+  const uint8_t* bytes;
+  __device__ __forceinline__ uint64_t key(int32_t i) const {
+    int32_t a = offs[i], b = offs[i + 1];
+    uint64_t k = 0;
+    for (int j = 0; j < 8; ++j) {
+      uint8_t c = (a + j < b) ? bytes[a + j] : 0;
+      k = (k << 8) | c;
+    }
+    return k;
+  }
+  // byte order of two strings whose prefix keys are equal: -1 / 0 / 1.
+  // Equal keys mean the first min(8, la, lb) bytes agree, so start there.
+  __device__ int tie(int32_t x, int32_t y) const {
+    int32_t ax = offs[x], ay = offs[y];
+    int32_t lx = offs[x + 1] - ax, ly = offs[y + 1] - ay;
+    int32_t m = lx < ly ? lx : ly;
+    for (int32_t j = m < 8 ? m : 8; j < m; ++j) {
+      uint8_t cx = bytes[ax + j], cy = bytes[ay + j];
+      if (cx != cy) return cx < cy ? -1 : 1;
+    }
+    return lx == ly ? 0 : (lx < ly ? -1 : 1);
+  }
+};
+
+struct Elem {
+  uint64_t key;
+  int32_t idx;    // global child index (-1 for padding)
+  uint32_t rank;  // null rank; RANK_PAD for padding
+};
+
+// vrank = rank of a valid element (1 under NULLS FIRST, 0 under NULLS LAST);
+// nulls take the other one and key 0
+template <typename Src>
+__device__ __forceinline__ Elem load_elem(const Src& src,
+                                          const uint64_t* cvalid, int32_t gi,
+                                          uint32_t vrank, int desc) {
+  Elem e;
+  e.idx = gi;
+  if (valid_bit(cvalid, gi)) {
+    uint64_t k = src.key(gi);
+    e.key = desc ? ~k : k;
+    e.rank = vrank;
+  } else {
+    e.key = 0;
+    e.rank = 1u - vrank;
+  }
+  return e;
+}
+
+template <typename Src>
+__device__ __forceinline__ bool elem_less(const Src& src, uint32_t ra,
+                                          uint64_t ka, int32_t ia,
+                                          uint32_t rb, uint64_t kb,
+                                          int32_t ib, uint32_t vrank,
+                                          int desc) {
+  if (ra != rb) return ra < rb;
+  if (ka != kb) return ka < kb;
+  if (ra == vrank) {
+    int c = src.tie(ia, ib);
+    if (c) return desc ? c > 0 : c < 0;
+  }
+  return ia < ib;
+}
+
+// ---- sub-wave tier: W lanes per list, bitonic over shuffles --------------
+
+__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m, int w) {
+  uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m, w);
+  uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m, w);
+  return ((uint64_t)hi << 32) | lo;
+}
+
+template <typename Src, int W>
+__global__ __launch_bounds__(HIPDF_BLOCK) void k_list_sort_wave(
+    Src src, const int32_t* __restrict__ offsets,
+    const uint64_t* __restrict__ cvalid, uint32_t vrank, int desc,
+    int32_t* __restrict__ perm, int64_t n) {
+  constexpr int L = WAVE / W;  // lists per wave
+  int lane = lane_id();
+  int sub = lane / W, sl = lane & (W - 1);
+  int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  int64_t nwaves = (int64_t)gridDim.x * blockDim.x / WAVE;
+  int32_t off0 = offsets[0];
+  // loop bounds are wave-uniform: every lane reaches every shuffle
+  for (int64_t base = wave * L; base < n; base += nwaves * L) {
+    int64_t row = base + sub;
+    int32_t start = 0, len = 0;
+    if (row < n) {
+      start = offsets[row];
+      len = offsets[row + 1] - start;
+    }
+    if (len > W) len = 0;  // longer rows belong to another tier
+    Elem e;
+    e.key = (uint64_t)sl;  // distinct keys keep the order strict among pads
+    e.idx = -1;
+    e.rank = RANK_PAD;
+    if (sl < len) e = load_elem(src, cvalid, start + sl, vrank, desc);
+#pragma unroll
+    for (int k = 2; k <= W; k <<= 1) {
+#pragma unroll
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        Elem o;
+        o.key = shfl_xor_u64(e.key, j, W);
+        o.idx = __shfl_xor(e.idx, j, W);
+        o.rank = (uint32_t)__shfl_xor((int)e.rank, j, W);
+        bool keep_min = ((sl & j) == 0) == ((sl & k) == 0);
+        bool o_less = elem_less(src, o.rank, o.key, o.idx, e.rank, e.key,
+                                e.idx, vrank, desc);
+        if (keep_min == o_less) e = o;
+      }
+    }
+    if (sl < len) perm[start - off0 + sl] = e.idx;
+  }
+}
+
+// ---- block tier: one block per list, bitonic in LDS ----------------------
+
+template <typename Src>
+__global__ __launch_bounds__(LIST_BLOCK) void k_list_sort_block(
+    Src src, const int32_t* __restrict__ offsets,
+    const uint64_t* __restrict__ cvalid, const int32_t* __restrict__ rows,
+    int64_t nrows, uint32_t vrank, int desc, int32_t* __restrict__ perm) {
+  __shared__ uint64_t skey[LIST_BLOCK_CAP];
+  __shared__ uint32_t spk[LIST_BLOCK_CAP];  // rank << 16 | local index
+  int tid = threadIdx.x;
+  int32_t off0 = offsets[0];
+  for (int64_t r = blockIdx.x; r < nrows; r += gridDim.x) {
+    int32_t row = rows[r];
+    int32_t start = offsets[row];
+    int32_t len = offsets[row + 1] - start;
+    if (len < 1 || len > LIST_BLOCK_CAP) continue;  // block-uniform
+    int P = 2;
+    while (P < len) P <<= 1;
+    for (int i = tid; i < P; i += LIST_BLOCK) {
+      if (i < len) {
+        Elem e = load_elem(src, cvalid, start + i, vrank, desc);
+        skey[i] = e.key;
+        spk[i] = (e.rank << 16) | (uint32_t)i;
+      } else {
+        skey[i] = 0;
+        spk[i] = (RANK_PAD << 16) | (uint32_t)i;
+      }
+    }
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1) {
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int i = tid; i < (P >> 1); i += LIST_BLOCK) {
+          int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1));
+          int hi = lo | j;
+          bool up = (lo & k) == 0;
+          uint64_t ka = skey[lo], kb = skey[hi];
+          uint32_t pa = spk[lo], pb = spk[hi];
+          bool b_less = elem_less(src, pb >> 16, kb,
+                                  start + (int32_t)(pb & 0xffffu), pa >> 16,
+                                  ka, start + (int32_t)(pa & 0xffffu), vrank,
+                                  desc);
+          if (b_less == up) {
+            skey[lo] = kb; skey[hi] = ka;
+            spk[lo] = pb; spk[hi] = pa;
+          }
+        }
+        __syncthreads();
+      }
+    }
+    for (int i = tid; i < len; i += LIST_BLOCK)
+      perm[start - off0 + i] = start + (int32_t)(spk[i] & 0xffffu);
+    __syncthreads();  // LDS is reused by the next row
+  }
+}
+
+// ---- distinct flags from an ascending sorted permutation -----------------
+// keep[orig - off0] = 0 when the element's predecessor in its own list (in
+// sorted order) has the same null rank and key; index tie-break in the sort
+// makes the survivor of each run the first occurrence.
+
+template <typename Src>
+__global__ void k_list_distinct_flags(Src src,
+                                      const int32_t* __restrict__ offsets,
+                                      int64_t n,
+                                      const uint64_t* __restrict__ cvalid,
+                                      const int32_t* __restrict__ perm,
+                                      uint8_t* __restrict__ keep,
+                                      int64_t total) {
+  int32_t off0 = offsets[0];
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total;
+       p += (int64_t)gridDim.x * blockDim.x) {
+    int32_t pos = off0 + (int32_t)p;
+    // last row r in [0, n) with offsets[r] <= pos (pos < offsets[n])
+    int64_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+      int64_t mid = (lo + hi) >> 1;
+      if (offsets[mid] <= pos) lo = mid; else hi = mid;
+    }
+    int32_t gi = perm[p];
+    bool dup = false;
+    if (pos != offsets[lo]) {
+      int32_t gj = perm[p - 1];
+      bool vi = valid_bit(cvalid, gi), vj = valid_bit(cvalid, gj);
+      if (vi != vj) dup = false;
+      else if (!vi) dup = true;
+      else dup = src.key(gi) == src.key(gj) && src.tie(gi, gj) == 0;
+    }
+    keep[gi - off0] = dup ? 0 : 1;
+  }
+}
+
+// ---- segmented arg-min / arg-max ignoring nulls --------------------------
+// W lanes stride over one list, then an xor-shuffle reduction. Result is the
+// global child index of the first least (greatest) element, or -1 for a
+// null / empty / all-null list.
+
+template <typename Src>
+__device__ __forceinline__ bool cand_better(const Src& src, uint64_t ka,
+                                            int32_t ia, uint64_t kb,
+                                            int32_t ib, int is_max) {
+  if (ka != kb) return ka < kb;  // key already inverted for max
+  int c = src.tie(ia, ib);
+  if (c) return is_max ? c > 0 : c < 0;
+  return ia < ib;
+}
+
+template <typename Src, int W>
+__global__ __launch_bounds__(HIPDF_BLOCK) void k_list_argminmax(
+    Src src, const int32_t* __restrict__ offsets,
+    const uint64_t* __restrict__ cvalid, const uint64_t* __restrict__ rvalid,
+    int is_max, int32_t* __restrict__ out, int64_t n) {
+  constexpr int L = WAVE / W;
+  int lane = lane_id();
+  int sub = lane / W, sl = lane & (W - 1);
+  int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  int64_t nwaves = (int64_t)gridDim.x * blockDim.x / WAVE;
+  for (int64_t base = wave * L; base < n; base += nwaves * L) {
+    int64_t row = base + sub;
+    int32_t start = 0, len = 0;
+    if (row < n && valid_bit(rvalid, row)) {
+      start = offsets[row];
+      len = offsets[row + 1] - start;
+    }
+    uint64_t bk = 0;
+    int32_t bi = -1;
+    for (int32_t i = sl; i < len; i += W) {
+      int32_t gi = start + i;
+      if (!valid_bit(cvalid, gi)) continue;
+      uint64_t k = src.key(gi);
+      if (is_max) k = ~k;
+      if (bi < 0 || cand_better(src, k, gi, bk, bi, is_max)) {
+        bk = k;
+        bi = gi;
+      }
+    }
+#pragma unroll
+    for (int j = W >> 1; j > 0; j >>= 1) {
+      uint64_t ok = shfl_xor_u64(bk, j, W);
+      int32_t oi = __shfl_xor(bi, j, W);
+      if (oi >= 0 && (bi < 0 || cand_better(src, ok, oi, bk, bi, is_max))) {
+        bk = ok;
+        bi = oi;
+      }
+    }
+    if (sl == 0 && row < n) out[row] = bi;
+  }
+}
+
+// ---- host side -----------------------------------------------------------
+
+template <typename F>
+static inline void dispatch_src(int t, const void* data, const void* eoffs,
+                                F&& f) {
+  if (t == LT_STR) {
+    f(StrSrc{(const int32_t*)eoffs, (const uint8_t*)data});
+  } else {
+    dispatch_type(t, [&]<typename T>() { f(FixedSrc<T>{(const T*)data}); });
+  }
+}
+
+template <typename F>
+static inline void dispatch_width(int w, F&& f) {
+  switch (w) {
+    case 8: f.template operator()<8>(); break;
+    case 16: f.template operator()<16>(); break;
+    case 32: f.template operator()<32>(); break;
+    case 64: f.template operator()<64>(); break;
+    default: throw std::runtime_error("hipdf: list group width not 8/16/32/64");
+  }
+}
+
+// one W-lane group per row, HIPDF_BLOCK threads per block, grid capped
+static inline dim3 group_grid(int64_t n, int w) {
+  int64_t per_block = (int64_t)HIPDF_BLOCK / w;
+  int64_t blocks = (n + per_block - 1) / per_block;
+  if (blocks > HIPDF_MAX_BLOCKS) blocks = HIPDF_MAX_BLOCKS;
+  if (blocks < 1) blocks = 1;
+  return dim3((uint32_t)blocks);
+}
+
+extern "C" {
+
+int hipdf_list_block_cap() { return LIST_BLOCK_CAP; }
+
+void hipdf_list_sort_wave(int t, const void* data, const void* eoffs,
+                          const void* cvalid, const void* offsets, int w,
+                          int nulls_first, int desc, void* perm, int64_t n,
+                          hipStream_t stream) {
+  if (n <= 0) return;
+  dispatch_src(t, data, eoffs, [&](auto src) {
+    using Src = decltype(src);
+    dispatch_width(w, [&]<int W>() {
+      hipLaunchKernelGGL((k_list_sort_wave<Src, W>), group_grid(n, W),
+                         dim3(HIPDF_BLOCK), 0, stream, src,
+                         (const int32_t*)offsets, (const uint64_t*)cvalid,
+                         (uint32_t)(nulls_first ? 1 : 0), desc,
+                         (int32_t*)perm, n);
+    });
+  });
+}
+
+void hipdf_list_sort_block(int t, const void* data, const void* eoffs,
+                           const void* cvalid, const void* offsets,
+                           const void* rows, int64_t nrows, int nulls_first,
+                           int desc, void* perm, hipStream_t stream) {
+  if (nrows <= 0) return;
+  int64_t blocks = nrows < HIPDF_MAX_BLOCKS ? nrows : HIPDF_MAX_BLOCKS;
+  dispatch_src(t, data, eoffs, [&](auto src) {
+    using Src = decltype(src);
+    hipLaunchKernelGGL((k_list_sort_block<Src>), dim3((uint32_t)blocks),
+                       dim3(LIST_BLOCK), 0, stream, src,
+                       (const int32_t*)offsets, (const uint64_t*)cvalid,
+                       (const int32_t*)rows, nrows,
+                       (uint32_t)(nulls_first ? 1 : 0), desc, (int32_t*)perm);
+  });
+}
+
+void hipdf_list_distinct_flags(int t, const void* data, const void* eoffs,
+                               const void* cvalid, const void* offsets,
+                               int64_t n, const void* perm, void* keep,
+                               int64_t total, hipStream_t stream) {
+  if (n <= 0 || total <= 0) return;
+  dispatch_src(t, data, eoffs, [&](auto src) {
+    using Src = decltype(src);
+    hipLaunchKernelGGL((k_list_distinct_flags<Src>), flat_grid(total),
+                       dim3(HIPDF_BLOCK), 0, stream, src,
+                       (const int32_t*)offsets, n, (const uint64_t*)cvalid,
+                       (const int32_t*)perm, (uint8_t*)keep, total);
+  });
+}
+
+void hipdf_list_argminmax(int t, const void* data, const void* eoffs,
+                          const void* cvalid, const void* offsets,
+                          const void* rvalid, int w, int is_max, void* out,
+                          int64_t n, hipStream_t stream) {
+  if (n <= 0) return;
+  dispatch_src(t, data, eoffs, [&](auto src) {
+    using Src = decltype(src);
+    dispatch_width(w, [&]<int W>() {
+      hipLaunchKernelGGL((k_list_argminmax<Src, W>), group_grid(n, W),
+                         dim3(HIPDF_BLOCK), 0, stream, src,
+                         (const int32_t*)offsets, (const uint64_t*)cvalid,
+                         (const uint64_t*)rvalid, is_max, (int32_t*)out, n);
+    });
+  });
+}
+
+}  // extern "C"

@@ -164,6 +164,29 @@ class Expression:
         array_contains; null list -> null)."""
         return ArrayContains(self, value)
 
+    def sort_array(self, asc: bool = True) -> "SortArray":
+        """Sort the elements of a LIST value (Spark sort_array): ascending
+        puts nulls first, descending puts them last; NaN is greatest."""
+        return SortArray(self, asc)
+
+    def array_sort(self) -> "ArraySort":
+        """Sort a LIST value ascending with nulls last (Spark array_sort,
+        default comparator)."""
+        return ArraySort(self)
+
+    def array_distinct(self) -> "ArrayDistinct":
+        """Drop duplicate elements of a LIST value, keeping each first
+        occurrence in place (Spark array_distinct)."""
+        return ArrayDistinct(self)
+
+    def array_min(self) -> "ArrayMin":
+        """Least non-null element of a LIST value (NaN greatest); NULL for
+        a null, empty or all-null list."""
+        return ArrayMin(self)
+
+    def array_max(self) -> "ArrayMax":
+        return ArrayMax(self)
+
     def regexp_extract(self, pattern: str, group: int = 1) -> "RegexpExtract":
         return RegexpExtract(self, pattern, group)
 
@@ -705,6 +728,112 @@ class ArraySize(Expression):
 
     def __str__(self):
         return f"size({self.child})"
+
+
+class SortArray(Expression):
+    """sort_array(array, asc): stable sort inside each list; ascending
+    puts nulls first, descending last (GpuSortArray analogue)."""
+
+    def __init__(self, child: Expression, ascending: bool = True):
+        self.child = child
+        self.ascending = bool(ascending)
+
+    @property
+    def children(self):
+        return (self.child,)
+
+    def dtype(self, schema: Schema) -> DType:
+        return self.child.dtype(schema)
+
+    def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
+        return ops.sort_array(self.child.eval(batch, schema),
+                              self.ascending, self.ascending)
+
+    def __str__(self):
+        return f"sort_array({self.child}, {str(self.ascending).lower()})"
+
+
+class ArraySort(Expression):
+    """array_sort(array): ascending, nulls last; default comparator only
+    (GpuArraySort analogue)."""
+
+    def __init__(self, child: Expression):
+        self.child = child
+
+    @property
+    def children(self):
+        return (self.child,)
+
+    def dtype(self, schema: Schema) -> DType:
+        return self.child.dtype(schema)
+
+    def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
+        return ops.sort_array(self.child.eval(batch, schema), True, False)
+
+    def __str__(self):
+        return f"array_sort({self.child})"
+
+
+class ArrayDistinct(Expression):
+    """array_distinct(array): first occurrences in input order, at most
+    one null (GpuArrayDistinct KEEP_FIRST)."""
+
+    def __init__(self, child: Expression):
+        self.child = child
+
+    @property
+    def children(self):
+        return (self.child,)
+
+    def dtype(self, schema: Schema) -> DType:
+        return self.child.dtype(schema)
+
+    def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
+        return ops.array_distinct(self.child.eval(batch, schema))
+
+    def __str__(self):
+        return f"array_distinct({self.child})"
+
+
+class ArrayMin(Expression):
+    """array_min(array): least non-null element, NaN greatest; NULL when
+    there is none (GpuArrayMin analogue)."""
+
+    def __init__(self, child: Expression):
+        self.child = child
+
+    @property
+    def children(self):
+        return (self.child,)
+
+    def dtype(self, schema: Schema) -> DType:
+        return self.child.dtype(schema).children[0]
+
+    def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
+        return ops.array_min(self.child.eval(batch, schema))
+
+    def __str__(self):
+        return f"array_min({self.child})"
+
+
+class ArrayMax(Expression):
+    """array_max(array): greatest non-null element (GpuArrayMax)."""
+
+    def __init__(self, child: Expression):
+        self.child = child
+
+    @property
+    def children(self):
+        return (self.child,)
+
+    def dtype(self, schema: Schema) -> DType:
+        return self.child.dtype(schema).children[0]
+
+    def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
+        return ops.array_max(self.child.eval(batch, schema))
+
+    def __str__(self):
+        return f"array_max({self.child})"
 
 
 class HostStringFn(Expression):

@@ -64,6 +64,28 @@ def element_at(col: Column, index: int) -> Column:
     return backend_for(col).element_at(col, index)
 
 
+def sort_array(col: Column, ascending: bool = True,
+               nulls_first: bool = True) -> Column:
+    """Stable sort inside each list by (null rank, value); NaN greatest,
+    null list -> null (GpuSortArray / GpuArraySort analogue)."""
+    return backend_for(col).sort_array(col, ascending, nulls_first)
+
+
+def array_distinct(col: Column) -> Column:
+    """First occurrence of each value per list, input order kept
+    (GpuArrayDistinct KEEP_FIRST)."""
+    return backend_for(col).array_distinct(col)
+
+
+def array_min(col: Column) -> Column:
+    """Least non-null element per list; NULL when there is none."""
+    return backend_for(col).array_min(col)
+
+
+def array_max(col: Column) -> Column:
+    return backend_for(col).array_max(col)
+
+
 def map_keys(col: Column) -> Column:
     """MAP -> LIST<key>: shares the offsets and the entry key child
     buffer (zero-copy, reference GpuMapKeys)."""

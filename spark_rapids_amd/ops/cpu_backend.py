@@ -676,6 +676,70 @@ def array_contains(col: Column, value) -> Column:
     return Column.from_pylist(out, DType.bool_())
 
 
+def _array_elem_key(x):
+    """Total order of non-null array elements (Spark's): NaN is greater
+    than every number and equal to itself, -0.0 equals 0.0, strings order
+    by their UTF-8 bytes. Ties keep input order wherever this key is used
+    (sorted/min/max are stable / first-occurrence)."""
+    if isinstance(x, float):
+        return (1, 0.0) if x != x else (0, x)
+    if isinstance(x, str):
+        return (0, x.encode("utf-8", "surrogatepass"))
+    return (0, x)
+
+
+def sort_array(col: Column, ascending: bool = True,
+               nulls_first: bool = True) -> Column:
+    """Stable sort inside each list; a null list stays null."""
+    out = []
+    for v in col.to_pylist():
+        if v is None:
+            out.append(None)
+            continue
+        nulls = [x for x in v if x is None]
+        vals = sorted((x for x in v if x is not None), key=_array_elem_key,
+                      reverse=not ascending)
+        out.append(nulls + vals if nulls_first else vals + nulls)
+    return Column.from_pylist(out, col.dtype)
+
+
+def array_distinct(col: Column) -> Column:
+    """First occurrence of every value in input order (KEEP_FIRST); at most
+    one null; NaN equals NaN and -0.0 equals 0.0."""
+    out = []
+    for v in col.to_pylist():
+        if v is None:
+            out.append(None)
+            continue
+        seen = set()
+        kept = []
+        for x in v:
+            k = None if x is None else _array_elem_key(x)
+            if k not in seen:
+                seen.add(k)
+                kept.append(x)
+        out.append(kept)
+    return Column.from_pylist(out, col.dtype)
+
+
+def _array_extreme(col: Column, pick) -> Column:
+    out = []
+    for v in col.to_pylist():
+        vals = [] if v is None else [x for x in v if x is not None]
+        out.append(pick(vals, key=_array_elem_key) if vals else None)
+    return Column.from_pylist(out, col.dtype.children[0])
+
+
+def array_min(col: Column) -> Column:
+    """Least non-null element (first occurrence); NULL for a null, empty
+    or all-null list."""
+    return _array_extreme(col, min)
+
+
+def array_max(col: Column) -> Column:
+    return _array_extreme(col, max)
+
+
 def map_get(col: Column, key) -> Column:
     out = []
     for v in col.to_pylist():  # dicts (last-win on duplicate keys)

@@ -776,6 +776,192 @@ def array_size(col: Column) -> Column:
                   null_count=col._null_count)
 
 
+# ---------------------------------------------------------------------------
+# lists: segmented sort / distinct / min / max (native/hipdf lists.hip)
+# ---------------------------------------------------------------------------
+_LT_STR = 7  # lists.hip element type id for a string child
+_LIST_WAVE_MAX = 64  # longest list the sub-wave tier sorts
+
+
+def _list_elem_args(elem: Column):
+    """(type id, data ptr, element offsets ptr) of a LIST child."""
+    if elem.dtype.id is TypeId.STRING:
+        return _LT_STR, elem.data.data_ptr(), elem.offsets.data_ptr()
+    return _ht(elem.dtype), elem.data.data_ptr(), 0
+
+
+def _list_group_width(maxlen: int) -> int:
+    w = 8
+    while w < maxlen and w < _LIST_WAVE_MAX:
+        w *= 2
+    return w
+
+
+def _list_bounds(col: Column):
+    """(first offset, child rows covered, int32 lengths column, longest
+    list) — one host sync each for the bounds and the maximum."""
+    n = col.size
+    off0, offn = (int(x) for x in col.offsets[0:n + 1:n].tolist())
+    a = Column(DType.int32(), n, col.offsets[1:n + 1], None, null_count=0)
+    b = Column(DType.int32(), n, col.offsets[:n], None, null_count=0)
+    lens = _binary("sub", a, b, None, DType.int32())
+    maxlen = int(reduce("max", lens) or 0)
+    return off0, offn - off0, lens, maxlen
+
+
+def _list_rebased_offsets(col: Column, off0: int) -> torch.Tensor:
+    n = col.size
+    if off0 == 0:
+        return col.offsets[:n + 1].clone()
+    oc = Column(DType.int32(), n + 1, col.offsets[:n + 1], None, null_count=0)
+    return binary_op_scalar("sub", oc, off0, DType.int32()).data
+
+
+def _list_with_child(col: Column, offsets: torch.Tensor,
+                     child: Column) -> Column:
+    v = col.validity.clone() if col.validity is not None else None
+    return Column(col.dtype, col.size,
+                  torch.zeros(0, dtype=torch.uint8, device="cuda"), v,
+                  offsets, col._null_count, child)
+
+
+def _list_sort_long(col: Column, lens: Column, cap: int, off0: int,
+                    ascending: bool, nulls_first: bool,
+                    perm: torch.Tensor) -> None:
+    """Lists longer than the block tier's cap: the global radix sort over
+    (row id, value) of only those rows, merged into `perm`. Index
+    bookkeeping of this rare tier is host-driven torch arithmetic."""
+    n = col.size
+    rows = mask_to_sel(binary_op_scalar("gt", lens, cap, DType.bool_()), n)
+    if rows.numel() == 0:
+        return
+    lr = rows.long()
+    offs = col.offsets[:n + 1].long()
+    starts = offs[lr]
+    cnt = offs[lr + 1] - starts
+    m = int(cnt.sum().item())
+    seg = torch.repeat_interleave(
+        torch.arange(lr.numel(), device="cuda", dtype=torch.int64), cnt)
+    base = torch.cumsum(cnt, 0) - cnt
+    eidx = (torch.arange(m, device="cuda", dtype=torch.int64)
+            - base[seg] + starts[seg]).to(torch.int32)
+    vals = _gather_col(col.child, eidx, m, maybe_negative=False)
+    segc = Column(DType.int32(), m, seg.to(torch.int32), None, null_count=0)
+    order = sort_order(ColumnBatch([segc, vals], m), [0, 1],
+                       [False, not ascending], [False, not nulls_first])
+    perm[eidx.long() - off0] = eidx[order.data.long()]
+
+
+def _list_sort_perm(col: Column, ascending: bool, nulls_first: bool):
+    """Permutation of global child indices that sorts every list in place:
+    (perm or None when no elements, first offset, elements covered)."""
+    n = col.size
+    s = _stream()
+    elem = col.child
+    off0, total, lens, maxlen = _list_bounds(col)
+    if total == 0:
+        return None, off0, 0
+    t, dp, eo = _list_elem_args(elem)
+    perm = torch.empty(total, dtype=torch.int32, device="cuda")
+    ext.list_sort_wave(t, dp, eo, _ptr(elem.validity),
+                       col.offsets.data_ptr(), _list_group_width(maxlen),
+                       nulls_first, not ascending, perm.data_ptr(), n, s)
+    if maxlen > _LIST_WAVE_MAX:
+        cap = ext.list_block_cap()
+        mid = binary_op(
+            "and", binary_op_scalar("gt", lens, _LIST_WAVE_MAX, DType.bool_()),
+            binary_op_scalar("le", lens, cap, DType.bool_()), DType.bool_())
+        rows = mask_to_sel(mid, n)
+        if rows.numel():
+            ext.list_sort_block(t, dp, eo, _ptr(elem.validity),
+                                col.offsets.data_ptr(), rows.data_ptr(),
+                                rows.numel(), nulls_first, not ascending,
+                                perm.data_ptr(), s)
+        if maxlen > cap:
+            _list_sort_long(col, lens, cap, off0, ascending, nulls_first,
+                            perm)
+    return perm, off0, total
+
+
+def sort_array(col: Column, ascending: bool = True,
+               nulls_first: bool = True) -> Column:
+    """Segmented stable sort of every list; the permutation goes through
+    the ordinary gather so validity and string bytes follow."""
+    n = col.size
+    if n == 0:
+        return Column.from_pylist([], col.dtype).cuda()
+    perm, off0, total = _list_sort_perm(col, ascending, nulls_first)
+    child = _gather_col(col.child, perm, total, maybe_negative=False) \
+        if total else _empty_col(col.child.dtype)
+    return _list_with_child(col, _list_rebased_offsets(col, off0), child)
+
+
+def array_distinct(col: Column) -> Column:
+    """Ascending segmented sort -> duplicate flags against the sorted
+    predecessor -> scan -> compaction in original order (KEEP_FIRST)."""
+    n = col.size
+    s = _stream()
+    if n == 0:
+        return Column.from_pylist([], col.dtype).cuda()
+    elem = col.child
+    perm, off0, total = _list_sort_perm(col, True, True)
+    if total == 0:
+        return _list_with_child(col, _list_rebased_offsets(col, off0),
+                                _empty_col(elem.dtype))
+    t, dp, eo = _list_elem_args(elem)
+    keep = torch.empty(total, dtype=torch.uint8, device="cuda")
+    ext.list_distinct_flags(t, dp, eo, _ptr(elem.validity),
+                            col.offsets.data_ptr(), n, perm.data_ptr(),
+                            keep.data_ptr(), total, s)
+    # kept-before counts at every element, one extra slot for the total
+    keep64 = torch.zeros(total + 1, dtype=torch.int64, device="cuda")
+    ext.cast(0, 4, keep.data_ptr(), keep64.data_ptr(), total, s)
+    scanned, nkept = _exclusive_scan_i64(keep64)
+    rebased = _list_rebased_offsets(col, off0)
+    offs64 = torch.empty(n + 1, dtype=torch.int64, device="cuda")
+    ext.gather_fixed(8, scanned.data_ptr(), rebased.data_ptr(),
+                     offs64.data_ptr(), n + 1, s)
+    new_offs = torch.empty(n + 1, dtype=torch.int32, device="cuda")
+    ext.narrow_i64_i32(offs64.data_ptr(), new_offs.data_ptr(), n + 1, s)
+    sel = mask_to_sel(Column(DType.bool_(), total, keep, None, null_count=0),
+                      total)
+    if off0:
+        sel = binary_op_scalar(
+            "add", Column(DType.int32(), nkept, sel, None, null_count=0),
+            off0, DType.int32()).data
+    child = _gather_col(elem, sel, nkept, maybe_negative=False)
+    return _list_with_child(col, new_offs, child)
+
+
+def _array_extreme(col: Column, is_max: bool) -> Column:
+    n = col.size
+    s = _stream()
+    elem = col.child
+    if n == 0:
+        return _empty_col(elem.dtype)
+    off0, total, _, maxlen = _list_bounds(col)
+    if total == 0:
+        idx = torch.full((n,), -1, dtype=torch.int32, device="cuda")
+    else:
+        t, dp, eo = _list_elem_args(elem)
+        idx = torch.empty(n, dtype=torch.int32, device="cuda")
+        ext.list_argminmax(t, dp, eo, _ptr(elem.validity),
+                           col.offsets.data_ptr(), _ptr(col.validity),
+                           _list_group_width(maxlen), is_max,
+                           idx.data_ptr(), n, s)
+    return _gather_col(elem, idx, n, maybe_negative=True)
+
+
+def array_min(col: Column) -> Column:
+    """Segmented arg-min over the sort keys (nulls skipped, NaN greatest),
+    then a nullable gather of the child."""
+    return _array_extreme(col, False)
+
+
+def array_max(col: Column) -> Column:
+    return _array_extreme(col, True)
+
+
 def substring(col: Column, pos: int, length: int = -1) -> Column:
     n = col.size
     s = _stream()

@@ -62,6 +62,11 @@ _GPU_STRING_UNARY = {"length", "upper", "lower", "trim", "ltrim",
                      "rtrim", "initcap", "reverse"}
 
 
+_ARRAY_FN_NAMES = {"SortArray": "sort_array", "ArraySort": "array_sort",
+                   "ArrayDistinct": "array_distinct",
+                   "ArrayMin": "array_min", "ArrayMax": "array_max"}
+
+
 class TagReason:
     def __init__(self, node: str, reasons: List[str]):
         self.node = node
@@ -154,6 +159,22 @@ class Tagger:
             et = e.child.dtype(schema).children[0]
             if et.is_nested:
                 out.append("array_contains over nested elements on CPU")
+        elif type(e).__name__ in ("SortArray", "ArraySort", "ArrayDistinct",
+                                  "ArrayMin", "ArrayMax"):
+            # segmented sort / distinct / arg-min-max kernels (lists.hip)
+            # cover fixed-width (<= 64 bit) and string elements
+            cdt = e.child.dtype(schema)
+            fn = _ARRAY_FN_NAMES[type(e).__name__]
+            if cdt.id is not TypeId.LIST:
+                out.append(f"{fn} needs an array input, got {cdt}")
+            else:
+                et = cdt.children[0]
+                if et.is_nested:
+                    out.append(f"{fn} over nested elements on CPU")
+                elif et.id is TypeId.DECIMAL128:
+                    out.append(f"{fn} over decimal128 elements on CPU")
+                elif not (et.is_fixed_width or et.id is TypeId.STRING):
+                    out.append(f"{fn} over {et} elements on CPU")
         elif type(e).__name__ in ("ArraySize", "ElementAt"):
             cdt = e.child.dtype(schema)
             if cdt.id is TypeId.MAP and type(e).__name__ == "ElementAt" \

@@ -715,6 +715,29 @@ class Parser:
             return ArrayContains(args[0], args[1].value
                                  if isinstance(args[1], Literal)
                                  else args[1])
+        if name == "sort_array":
+            from ..expr.expressions import Literal, SortArray
+
+            asc = True
+            if len(args) > 1:
+                if not (isinstance(args[1], Literal)
+                        and isinstance(args[1].value, bool)):
+                    raise ValueError(
+                        "sort_array(a, asc): asc must be a boolean literal")
+                asc = args[1].value
+            return SortArray(args[0], asc)
+        if name in ("array_sort", "array_distinct", "array_min",
+                    "array_max"):
+            from ..expr import expressions as _ex
+
+            if len(args) != 1:
+                raise ValueError(f"{name} takes one argument "
+                                 "(comparator lambdas are not supported)")
+            cls = {"array_sort": _ex.ArraySort,
+                   "array_distinct": _ex.ArrayDistinct,
+                   "array_min": _ex.ArrayMin,
+                   "array_max": _ex.ArrayMax}[name]
+            return cls(args[0])
         if name in ("map_keys", "map_values", "map_entries"):
             from ..expr.expressions import MapView
 

@@ -182,7 +182,15 @@ _EXPR_ROWS = [
     ("Explode_outer", "explode(outer=True)", "CPU", "padding path"),
     ("Size", "ArraySize", "GPU", ""),
     ("ElementAt (array)", "ElementAt", "GPU", "1-based, NULL overflow"),
-    ("SortArray", "-", "CPU", ""),
+    ("SortArray", "sort_array / col.sort_array(asc)", "GPU",
+     "segmented bitonic sort (lists.hip); decimal128/nested elements CPU"),
+    ("ArraySort", "array_sort", "GPU",
+     "ascending, nulls last; default comparator only (no lambda)"),
+    ("ArrayDistinct", "array_distinct", "GPU",
+     "first occurrences kept in place; decimal128/nested elements CPU"),
+    ("ArrayMin", "array_min", "GPU",
+     "segmented arg-min, nulls skipped, NaN greatest"),
+    ("ArrayMax", "array_max", "GPU", "segmented arg-max"),
     ("CreateArray", "from_pylist lists", "CPU", "construction host-side"),
     # misc
     ("Rand", "SampleHash deterministic draw", "GPU", "sample() lowering"),
