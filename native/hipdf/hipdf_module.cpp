@@ -11,6 +11,9 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <vector>
+
+#include "kernels/sort_desc.h"
 
 namespace py = pybind11;
 
@@ -53,6 +56,8 @@ void hipdf_copy_valid_range(const void*, int, int64_t, void*, int64_t,
 int64_t scan_num_blocks(int64_t);
 void hipdf_scan_block(const void*, void*, void*, int64_t, hipStream_t);
 void hipdf_scan_add_offsets(void*, const void*, int64_t, hipStream_t);
+int64_t scan_scratch_elems(int64_t);
+void hipdf_exclusive_scan_i64(const void*, void*, void*, int64_t, hipStream_t);
 void hipdf_reduce(int, int, const void*, const void*, void*, void*, int64_t,
                   hipStream_t);
 void hipdf_murmur3_col(int, int, const void*, const void*, const void*,
@@ -216,6 +221,8 @@ void hipdf_make_sort_keys_i128(const void*, const void*, const void*, int,
 void hipdf_radix_count(const void*, int, void*, int64_t, hipStream_t);
 void hipdf_radix_scatter(const void*, const void*, int, const void*, void*,
                          void*, int64_t, hipStream_t);
+void hipdf_sort_order(const HipdfSortKey*, int, int64_t, void*, void*, void*,
+                      void*, void*, void*, void*, void*, void*, hipStream_t);
 void hipdf_part_hist(const void*, int, void*, int64_t, hipStream_t);
 void hipdf_part_scatter(const void*, int, const void*, void*, int64_t,
                         hipStream_t);
@@ -734,6 +741,13 @@ PYBIND11_MODULE(hipdf, m) {
     hipdf_scan_add_offsets(PM(out), P(sums), n, S(stream));
     check_async();
   });
+  m.def("scan_scratch_elems", &scan_scratch_elems);
+  // every level of the scan in one call; the total lands in scratch[-1]
+  m.def("exclusive_scan_i64", [](int64_t in, int64_t out, int64_t scratch,
+                                 int64_t n, int64_t stream) {
+    hipdf_exclusive_scan_i64(P(in), PM(out), PM(scratch), n, S(stream));
+    check_async();
+  });
   m.def("reduce", [](int op, int t, int64_t a, int64_t av, int64_t acc,
                      int64_t cnt, int64_t n, int64_t stream) {
     hipdf_reduce(op, t, P(a), P(av), PM(acc), PM(cnt), n, S(stream));
@@ -1227,6 +1241,40 @@ PYBIND11_MODULE(hipdf, m) {
                              int64_t keys, int64_t n, int64_t stream) {
     hipdf_make_sort_keys(t, P(data), P(valid), P(perm), desc, nulls_last,
                          null_only, PM(keys), n, S(stream));
+    check_async();
+  });
+  // keys: one tuple per sort key, most significant first:
+  // (kind, htype, data, valid, offsets, desc, nulls_last, has_valid, nchunks)
+  m.def("sort_order", [](const std::vector<py::tuple>& keys, int64_t n,
+                         int64_t keys_a, int64_t keys_b, int64_t perm_a,
+                         int64_t perm_b, int64_t counts, int64_t scanned,
+                         int64_t scan_scratch, int64_t diff, int64_t out_perm,
+                         int64_t stream) {
+    std::vector<HipdfSortKey> ks;
+    ks.reserve(keys.size());
+    for (const py::tuple& t : keys) {
+      if (t.size() != 9) throw std::runtime_error("hipdf: bad sort key");
+      HipdfSortKey k;
+      k.kind = t[0].cast<int32_t>();
+      k.htype = t[1].cast<int32_t>();
+      k.data = P(t[2].cast<int64_t>());
+      k.valid = P(t[3].cast<int64_t>());
+      k.offsets = P(t[4].cast<int64_t>());
+      k.desc = t[5].cast<bool>();
+      k.nulls_last = t[6].cast<bool>();
+      k.has_valid = t[7].cast<bool>();
+      k.nchunks = t[8].cast<int32_t>();
+      if (k.kind < SORT_KEY_FIXED || k.kind > SORT_KEY_DECIMAL128 ||
+          (k.kind == SORT_KEY_STRING && k.nchunks < 1))
+        throw std::runtime_error("hipdf: bad sort key");
+      ks.push_back(k);
+    }
+    {
+      py::gil_scoped_release nogil;
+      hipdf_sort_order(ks.data(), (int)ks.size(), n, PM(keys_a), PM(keys_b),
+                       PM(perm_a), PM(perm_b), PM(counts), PM(scanned),
+                       PM(scan_scratch), PM(diff), PM(out_perm), S(stream));
+    }
     check_async();
   });
   m.def("radix_count", [](int64_t keys, int shift, int64_t counts, int64_t n,

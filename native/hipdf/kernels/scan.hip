@@ -1,6 +1,10 @@
 // Device-wide exclusive scan (int64) + whole-column reductions.
-// Scan is the 3-phase scheme: block-local scan emitting per-block sums,
-// python recursively scans the (small) sums array, then an add-offsets pass.
+// Scan is the 3-phase scheme: block-local scan emitting per-block sums, a
+// scan of the (small) sums array, then an add-offsets pass.
+// hipdf_exclusive_scan_i64 enqueues every level in one call (level sizes come
+// from n on the host, nothing synchronises) and leaves the grand total in the
+// last element of its scratch; the single-level entries stay for callers that
+// drive the levels themselves.
 // Used by: filter compaction, string gather offsets, join match offsets,
 // partition offsets. Reductions: wave shfl -> LDS -> one device atomic per
 // block (guide §6 G12).
@@ -8,10 +12,21 @@
 
 #define SCAN_ITEMS 8  // elements per thread
 
+// A non-null `skip` names a u64 word of varying key bits (sort.hip): when its
+// byte at `skip_shift` is zero the radix pass moves nothing, its counts are
+// not read, and both scan kernels return at once.
+__device__ __forceinline__ bool scan_skipped(const uint64_t* skip,
+                                             int skip_shift) {
+  return skip && ((*skip >> skip_shift) & 255ull) == 0;
+}
+
 // exclusive block scan of in[base .. base+2048) -> out, block sum -> sums
 __global__ void k_scan_block(const int64_t* __restrict__ in,
                              int64_t* __restrict__ out,
-                             int64_t* __restrict__ sums, int64_t n) {
+                             int64_t* __restrict__ sums, int64_t n,
+                             const uint64_t* __restrict__ skip,
+                             int skip_shift) {
+  if (scan_skipped(skip, skip_shift)) return;
   __shared__ int64_t wave_sums[HIPDF_BLOCK / WAVE];
   int64_t base = (int64_t)blockIdx.x * HIPDF_BLOCK * SCAN_ITEMS;
   int tid = threadIdx.x;
@@ -57,7 +72,10 @@ __global__ void k_scan_block(const int64_t* __restrict__ in,
 
 __global__ void k_scan_add_offsets(int64_t* __restrict__ out,
                                    const int64_t* __restrict__ scanned_sums,
-                                   int64_t n) {
+                                   int64_t n,
+                                   const uint64_t* __restrict__ skip,
+                                   int skip_shift) {
+  if (scan_skipped(skip, skip_shift)) return;
   int64_t off = scanned_sums[blockIdx.x];
   int64_t base = (int64_t)blockIdx.x * HIPDF_BLOCK * SCAN_ITEMS;
   for (int k = 0; k < SCAN_ITEMS; ++k) {
@@ -153,7 +171,7 @@ void hipdf_scan_block(const void* in, void* out, void* sums, int64_t n,
   int64_t nb = scan_num_blocks(n);
   hipLaunchKernelGGL(k_scan_block, dim3((uint32_t)nb), dim3(HIPDF_BLOCK), 0,
                      stream, (const int64_t*)in, (int64_t*)out, (int64_t*)sums,
-                     n);
+                     n, (const uint64_t*)nullptr, 0);
 }
 
 void hipdf_scan_add_offsets(void* out, const void* scanned_sums, int64_t n,
@@ -161,7 +179,49 @@ void hipdf_scan_add_offsets(void* out, const void* scanned_sums, int64_t n,
   int64_t nb = scan_num_blocks(n);
   hipLaunchKernelGGL(k_scan_add_offsets, dim3((uint32_t)nb),
                      dim3(HIPDF_BLOCK), 0, stream, (int64_t*)out,
-                     (const int64_t*)scanned_sums, n);
+                     (const int64_t*)scanned_sums, n,
+                     (const uint64_t*)nullptr, 0);
+}
+
+// scratch elements hipdf_exclusive_scan_i64 needs for n inputs: per level
+// above the first, the block sums and their scan; the top level's single
+// block sum (the grand total) comes last.
+int64_t scan_scratch_elems(int64_t n) {
+  int64_t elems = 0;
+  for (int64_t m = scan_num_blocks(n); m > 1; m = scan_num_blocks(m))
+    elems += 2 * m;
+  return elems + 1;
+}
+
+// All levels of the exclusive scan of in[0, n) -> out, enqueued on `stream`
+// without synchronising. scratch holds scan_scratch_elems(n) int64; its last
+// element receives the grand total. `skip` / `skip_shift`: see scan_skipped.
+void hipdf_exclusive_scan_i64_skip(const void* in, void* out, void* scratch,
+                                   int64_t n, const void* skip,
+                                   int skip_shift, hipStream_t stream) {
+  int64_t* sc = (int64_t*)scratch;
+  if (n <= 0) {
+    (void)hipMemsetAsync(sc, 0, sizeof(int64_t), stream);
+    return;
+  }
+  int64_t nb = scan_num_blocks(n);
+  hipLaunchKernelGGL(k_scan_block, dim3((uint32_t)nb), dim3(HIPDF_BLOCK), 0,
+                     stream, (const int64_t*)in, (int64_t*)out, sc, n,
+                     (const uint64_t*)skip, skip_shift);
+  if (nb > 1) {
+    // sums at sc[0, nb), their scan at sc[nb, 2nb), upper levels after
+    hipdf_exclusive_scan_i64_skip(sc, sc + nb, sc + 2 * nb, nb, skip,
+                                  skip_shift, stream);
+    hipLaunchKernelGGL(k_scan_add_offsets, dim3((uint32_t)nb),
+                       dim3(HIPDF_BLOCK), 0, stream, (int64_t*)out,
+                       (const int64_t*)(sc + nb), n, (const uint64_t*)skip,
+                       skip_shift);
+  }
+}
+
+void hipdf_exclusive_scan_i64(const void* in, void* out, void* scratch,
+                              int64_t n, hipStream_t stream) {
+  hipdf_exclusive_scan_i64_skip(in, out, scratch, n, nullptr, 0, stream);
 }
 
 void hipdf_reduce(int op, int t, const void* a, const void* av, void* acc,

@@ -1279,14 +1279,12 @@ def _exclusive_scan_i64(vals: torch.Tensor) -> Tuple[torch.Tensor, int]:
     if n == 0:
         return vals, 0
     out = torch.empty(n, dtype=torch.int64, device="cuda")
-    nb = ext.scan_num_blocks(n)
-    sums = torch.empty(nb, dtype=torch.int64, device="cuda")
-    ext.scan_block(vals.data_ptr(), out.data_ptr(), sums.data_ptr(), n, s)
-    if nb > 1:
-        scanned_sums, total = _exclusive_scan_i64(sums)
-        ext.scan_add_offsets(out.data_ptr(), scanned_sums.data_ptr(), n, s)
-        return out, total
-    return out, int(sums[0].item())
+    scratch = torch.empty(ext.scan_scratch_elems(n), dtype=torch.int64,
+                          device="cuda")
+    # every level in one native call; the grand total is scratch's last slot
+    ext.exclusive_scan_i64(vals.data_ptr(), out.data_ptr(),
+                           scratch.data_ptr(), n, s)
+    return out, int(scratch[-1].item())
 
 
 # ---------------------------------------------------------------------------
@@ -2194,6 +2192,10 @@ def join_gather_maps(left: ColumnBatch, right: ColumnBatch,
 # sort: stable LSD radix over order-preserving u64 keys (native/hipdf sort.hip)
 # ---------------------------------------------------------------------------
 
+# HipdfSortKind of native/hipdf/kernels/sort_desc.h
+_SORT_KEY_FIXED, _SORT_KEY_STRING, _SORT_KEY_DECIMAL128 = 0, 1, 2
+
+
 def range_key(col: Column, desc: bool, nulls_last: bool) -> Column:
     """Monotone int64 proxy of the sort position of each row (signed order;
     ties allowed). Used by external sort to range-partition rows into
@@ -2231,42 +2233,15 @@ def sort_order(batch: ColumnBatch, key_idx: List[int], descending: List[bool],
     s = _stream()
     if n == 0:
         return _empty_col(DType.int32())
-    perm: Optional[torch.Tensor] = None
-    keys_a = torch.empty(n, dtype=torch.int64, device="cuda")
-    keys_b = torch.empty(n, dtype=torch.int64, device="cuda")
-    perm_a = torch.empty(n, dtype=torch.int32, device="cuda")
-    perm_b = torch.empty(n, dtype=torch.int32, device="cuda")
-    nb = ext.sort_num_blocks(n)
-    counts = torch.empty(256 * nb, dtype=torch.int64, device="cuda")
-    # least-significant key first: stability carries earlier orders forward
-    for ci, desc, nl in reversed(list(zip(key_idx, descending, nulls_last))):
+    # key descriptors for the native call, most significant first:
+    # (kind, htype, data, valid, offsets, desc, nulls_last, has_valid, nchunks)
+    descs = []
+    for ci, desc, nl in zip(key_idx, descending, nulls_last):
         col = batch.columns[ci]
-        wide = col.dtype.id in (TypeId.STRING, TypeId.DECIMAL128)
-        t = 4 if wide else _ht(col.dtype)
         has_valid = col.validity is not None
-        vwidth = ext.sort_key_width(t)
-        embedded_null = vwidth < 8  # null byte fits above the value bytes
-
-        cur_keys, alt_keys = keys_a, keys_b
-        cur_perm, alt_perm = perm, perm_a if perm is not perm_a else perm_b
-
-        def _passes(npasses, shift0=0):
-            nonlocal cur_keys, alt_keys, cur_perm, alt_perm
-            for p in range(npasses):
-                sh = 8 * (shift0 + p)
-                ext.radix_count(cur_keys.data_ptr(), sh, counts.data_ptr(), n, s)
-                offsets, _ = _exclusive_scan_i64(counts)
-                ext.radix_scatter(cur_keys.data_ptr(),
-                                  0 if cur_perm is None else cur_perm.data_ptr(),
-                                  sh, offsets.data_ptr(), alt_keys.data_ptr(),
-                                  alt_perm.data_ptr(), n, s)
-                cur_keys, alt_keys = alt_keys, cur_keys
-                nxt = perm_b if alt_perm is perm_a else perm_a
-                cur_perm, alt_perm = alt_perm, nxt
-
         if col.dtype.id is TypeId.STRING:
-            # LSD over 8-byte big-endian chunks, last chunk first; the
-            # stable radix carries earlier chunk orders forward
+            # LSD over 8-byte big-endian chunks: the host needs the longest
+            # string to know how many chunks there are
             lens = Column(DType.int32(), n, col.offsets[1:], None,
                           null_count=0)
             starts0 = Column(DType.int32(), n, col.offsets[:n], None,
@@ -2274,38 +2249,33 @@ def sort_order(batch: ColumnBatch, key_idx: List[int], descending: List[bool],
             ldiff = _binary("sub", lens, starts0, None, DType.int32())
             maxlen = reduce("max", ldiff) or 0
             nchunks = max(1, (int(maxlen) + 7) // 8)
-            for chunk in range(nchunks - 1, -1, -1):
-                ext.make_sort_keys_str(
-                    col.offsets.data_ptr(), col.data.data_ptr(),
-                    _ptr(col.validity),
-                    0 if cur_perm is None else cur_perm.data_ptr(), desc,
-                    chunk, cur_keys.data_ptr(), n, s)
-                _passes(8)
+            descs.append((_SORT_KEY_STRING, 4, col.data.data_ptr(),
+                          _ptr(col.validity), col.offsets.data_ptr(),
+                          bool(desc), bool(nl), has_valid, nchunks))
         elif col.dtype.id is TypeId.DECIMAL128:
-            for word in (0, 1):  # lo (unsigned) then hi (sign-biased)
-                ext.make_sort_keys_i128(
-                    col.data.data_ptr(), _ptr(col.validity),
-                    0 if cur_perm is None else cur_perm.data_ptr(), desc,
-                    word, cur_keys.data_ptr(), n, s)
-                _passes(8)
+            descs.append((_SORT_KEY_DECIMAL128, 4, col.data.data_ptr(),
+                          _ptr(col.validity), 0, bool(desc), bool(nl),
+                          has_valid, 0))
         else:
-            ext.make_sort_keys(t, col.data.data_ptr(), _ptr(col.validity),
-                               0 if cur_perm is None else cur_perm.data_ptr(),
-                               desc, nl, False, cur_keys.data_ptr(), n, s)
-            _passes(vwidth + (1 if (has_valid and embedded_null) else 0))
-        wide_key = col.dtype.id in (TypeId.STRING, TypeId.DECIMAL128) \
-            or not embedded_null
-        if has_valid and wide_key:
-            # no embedded null byte: one extra null-ordering pass
-            ext.make_sort_keys(4, col.data.data_ptr(), _ptr(col.validity),
-                               0 if cur_perm is None else cur_perm.data_ptr(),
-                               desc, nl, True, cur_keys.data_ptr(), n, s)
-            _passes(1)
-        perm = cur_perm
-        keys_a, keys_b = cur_keys, alt_keys
-    if perm is None:
-        perm = torch.arange(n, dtype=torch.int32, device="cuda")
-    return Column(DType.int32(), n, perm.clone(), None, null_count=0)
+            descs.append((_SORT_KEY_FIXED, _ht(col.dtype),
+                          col.data.data_ptr(), _ptr(col.validity), 0,
+                          bool(desc), bool(nl), has_valid, 0))
+    ncounts = 256 * ext.sort_num_blocks(n)
+    # scratch of the whole sort in two allocations: u64 keys x2, counts,
+    # their scan, the scan's own scratch and the varying-bits word; i32 perms
+    nscan = ext.scan_scratch_elems(ncounts)
+    w64 = torch.empty(2 * n + 2 * ncounts + nscan + 1, dtype=torch.int64,
+                      device="cuda")
+    w32 = torch.empty(2 * n, dtype=torch.int32, device="cuda")
+    perm = torch.empty(n, dtype=torch.int32, device="cuda")
+    p64, p32 = w64.data_ptr(), w32.data_ptr()
+    counts_p = p64 + 16 * n
+    scanned_p = counts_p + 8 * ncounts
+    scratch_p = scanned_p + 8 * ncounts
+    ext.sort_order(descs, n, p64, p64 + 8 * n, p32, p32 + 4 * n, counts_p,
+                   scanned_p, scratch_p, scratch_p + 8 * nscan,
+                   perm.data_ptr(), s)
+    return Column(DType.int32(), n, perm, None, null_count=0)
 
 
 def str_pad(col: Column, width: int, fill: str, left: bool) -> Column:

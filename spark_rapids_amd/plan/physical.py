@@ -1213,17 +1213,21 @@ class TopNExec(PhysicalExec):
         kidx = [self.schema.index(k) for k in self.keys]
         order = ops.sort_order(batch, kidx, self.descending,
                                self.nulls_last)
-        taken = ops.gather(batch, order)
-        return _slice_rows(taken, 0, min(self.n, taken.num_rows)) \
-            if taken.num_rows > self.n else taken
+        # gather only the survivors: the first n entries of the permutation
+        # (a permutation has no negative index, so no masks materialise)
+        k = min(self.n, batch.num_rows)
+        head = Column(order.dtype, k, order.data[:k], None, null_count=0)
+        return ops.gather(batch, head, negatives=False)
 
     def execute(self) -> Iterator[ColumnBatch]:
         heads = [self._sort_head(b)
                  for b in self.children[0].execute() if b.num_rows]
         if not heads:
             return
-        merged = ops.concat_batches(heads) if len(heads) > 1 else heads[0]
-        yield self._sort_head(merged)
+        if len(heads) == 1:
+            yield heads[0]  # already the sorted head: nothing to merge
+            return
+        yield self._sort_head(ops.concat_batches(heads))
 
     def describe(self):
         ks = ", ".join(f"{k}{' DESC' if d else ''}"
