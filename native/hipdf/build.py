@@ -16,6 +16,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 BUILD = os.path.join(HERE, "build")
+INCLUDE = os.path.join(HERE, "include")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
@@ -55,8 +56,9 @@ def _newer(src, obj):
     if not os.path.exists(obj):
         return True
     common = os.path.join(HERE, "kernels")
-    deps = [src] + [os.path.join(common, h)
-                    for h in os.listdir(common) if h.endswith(".h")]
+    deps = [src, os.path.join(INCLUDE, "hipdf.h")] + \
+        [os.path.join(common, h)
+         for h in os.listdir(common) if h.endswith(".h")]
     return any(os.path.getmtime(d) > os.path.getmtime(obj) for d in deps)
 
 
@@ -66,7 +68,7 @@ def _compile_one(src_rel: str) -> str:
     if not _newer(src, obj):
         return obj
     cmd = [HIPCC, "-c", "-x", "hip", src, "-o", obj] + CXXFLAGS + \
-        [f"-I{os.path.join(HERE, 'kernels')}"]
+        [f"-I{os.path.join(HERE, 'kernels')}", f"-I{INCLUDE}"]
     subprocess.run(cmd, check=True)
     return obj
 
@@ -86,7 +88,7 @@ def build(verbose: bool = True) -> str:
     mod_obj = os.path.join(BUILD, "hipdf_module.o")
     if _newer(mod_src, mod_obj):
         subprocess.run([HIPCC, "-c", mod_src, "-o", mod_obj] + CXXFLAGS +
-                       _pybind_includes(), check=True)
+                       [f"-I{INCLUDE}"] + _pybind_includes(), check=True)
     out = ext_path()
     link_inputs = objs + [mod_obj]
     if not os.path.exists(out) or any(
@@ -107,7 +109,7 @@ def build(verbose: bool = True) -> str:
             not os.path.exists(ctest_bin)
             or os.path.getmtime(ctest_src) > os.path.getmtime(ctest_bin)
             or os.path.getmtime(libso) > os.path.getmtime(ctest_bin)):
-        subprocess.run([HIPCC, f"-I{os.path.join(HERE, 'include')}",
+        subprocess.run([HIPCC, f"-I{INCLUDE}",
                         ctest_src, f"-L{REPO}", "-lhipdf",
                         f"-Wl,-rpath,$ORIGIN", "-o", ctest_bin,
                         f"--offload-arch={ARCH}"], check=True)

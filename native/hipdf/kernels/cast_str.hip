@@ -10,6 +10,7 @@
 //
 // decimal -> string: fixed-scale formatting with trailing zeros
 // ("1.50" for decimal(_,2)), two-pass lengths/write like k_i64_to_str.
+#include "hipdf.h"
 #include "hipdf_common.h"
 
 typedef unsigned __int128 u128;

@@ -3,6 +3,7 @@
 // place: int64 / float64 / date days / raw string spans. Quoted fields
 // bump `unsupported` and the host falls back to the CPU reader for the
 // file (exactness over a half-implemented dialect).
+#include "hipdf.h"
 #include "hipdf_common.h"
 
 __global__ void k_byte_eq(const uint8_t* __restrict__ bytes, uint8_t target,

@@ -2,6 +2,7 @@
 // (reference analogue: spark-rapids-jni GpuTimeZoneDB), and fixed-width
 // date_format / timestamp parse driven by a compiled token program
 // (reference analogue: the datetimeExpressions format family).
+#include "hipdf.h"
 #include "hipdf_common.h"
 
 __device__ __forceinline__ int64_t floor_div_dt(int64_t a, int64_t b) {

@@ -1,6 +1,7 @@
 // 128-bit decimal kernels (reference analogue: spark-rapids-jni Arithmetic
 // — decimal128 add/sub/compare — SURVEY.md §2.8B). Layout: interleaved
 // little-endian (lo, hi) int64 word pairs per row (arrow decimal128 LE).
+#include "hipdf.h"
 #include "hipdf_common.h"
 
 struct i128 {

@@ -7,6 +7,7 @@
 // One workgroup decodes one page's RLE stream: lane 0 walks run headers
 // (varint), the whole block expands runs in parallel (RLE fill / bit-packed
 // unpack, LSB-first as parquet specifies).
+#include "hipdf.h"
 #include "hipdf_common.h"
 
 // decode an RLE/bit-packed hybrid stream of n_values values of bit_width

@@ -4,6 +4,7 @@
 // bitmask write is free (one store per 64 rows). Null semantics implemented
 // in-kernel: div/mod by zero -> NULL, log(<=0) -> NULL, Kleene AND/OR,
 // NaN==NaN true and NaN greatest (Spark ordering).
+#include "hipdf.h"
 #include "hipdf_common.h"
 #include <math.h>
 

@@ -12,6 +12,7 @@
 //      in LDS, one device atomic per (block, group) at flush — this is what
 //      makes 4-group q1-style aggregations run at HBM bandwidth instead of
 //      serializing on 4 hot atomics.
+#include "hipdf.h"
 #include "hipdf_common.h"
 #include "keys.h"
 
@@ -61,15 +62,7 @@ __global__ void k_gb_build(const int32_t* __restrict__ hashes,
 // leader gather. gid = sum_i code_i * stride_i with code_i = key_i - min_i
 // (range_i for NULL, so nulls group together). Empty ids are compacted by
 // the host afterwards.
-struct DenseKey {
-  int type;        // HType of the key column
-  int pad;
-  const void* vals;
-  const uint64_t* valid;
-  int64_t kmin;
-  int64_t range;   // #distinct slots for values; NULL takes index `range`
-  int64_t stride;
-};
+using DenseKey = HipdfDenseKey;
 
 __device__ __forceinline__ int64_t dense_load_i64(const void* p, int t,
                                                   int64_t i) {
@@ -238,20 +231,7 @@ __global__ void k_gb_agg(int op, const T* __restrict__ vals,
 
 // ---- fused multi-aggregate: one pass over row_gid and every value column
 // (saves one full re-read of row_gid + one kernel launch per aggregate) ----
-struct AggDesc {
-  int op;             // GbOp
-  int type;           // HType of the value column
-  int acc_is_double;  // accumulator: double (1) or int64 (0)
-  int skip_cnt;       // sum/min/max over a non-null column: the count
-                      // atomic is pure overhead (group validity is
-                      // implied by group existence) — skip it in the
-                      // global-atomic path; the LDS path still counts
-                      // (its flush is gated on lcnt)
-  const void* vals;
-  const uint64_t* valid;
-  void* acc;          // [ngroups] double or int64
-  int64_t* cnt;       // [ngroups]
-};
+using AggDesc = HipdfAggDesc;
 
 __device__ __forceinline__ double load_as_double(const void* p, int t,
                                                  int64_t i) {

@@ -3,6 +3,7 @@
 // (spark_rapids_amd/ops/cpu_backend.py murmur3_hash) and to Spark's
 // Murmur3Hash so GPU shuffle partitioning lines up with CPU Spark
 // (reference analogue: spark-rapids-jni Hash.murmurHash32 — SURVEY.md §2.8B).
+#include "hipdf.h"
 #include "hipdf_common.h"
 #include "murmur3.h"
 

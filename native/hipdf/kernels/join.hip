@@ -7,6 +7,7 @@
 //
 // Chained table: head[slot] -> newest row, next[row] -> older row in bucket.
 // Duplicates and collisions live on the chain; equality filters on probe.
+#include "hipdf.h"
 #include "hipdf_common.h"
 #include "keys.h"
 #include "murmur3.h"

@@ -3,15 +3,10 @@
 // Spark semantics: NULL == NULL for grouping (nulls form one group),
 // NaN == NaN, -0.0 == 0.0.
 #pragma once
+#include "hipdf.h"
 #include "hipdf_common.h"
 
-struct KeyCol {
-  int type;        // HType
-  int is_string;   // 1 -> data=offsets(int32*), aux=bytes(uint8*)
-  const void* data;
-  const uint64_t* valid;
-  const void* aux;
-};
+using KeyCol = HipdfKeyCol;
 
 __device__ __forceinline__ bool keyval_equal(const KeyCol& c, int64_t ra,
                                              const KeyCol& cb, int64_t rb) {

@@ -20,6 +20,7 @@
 //   <= 2048  one 256-thread block per list, bitonic in LDS over
 //            (u64 key, u32 rank|local index) = 24 KB at the cap
 //   longer   host routes those rows through the global radix sort
+#include "hipdf.h"
 #include "hipdf_common.h"
 #include "sort_keys.h"
 

@@ -5,6 +5,7 @@
 // laid out part-major so a single flat exclusive scan yields scatter
 // offsets (classic radix-partition scheme). Also used as one digit pass
 // of the LSD radix sort.
+#include "hipdf.h"
 #include "hipdf_common.h"
 
 #define PART_MAX_LDS 4096  // max partitions held in LDS (16 KiB of int32)

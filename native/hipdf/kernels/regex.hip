@@ -6,6 +6,7 @@
 // One thread per row; explicit backtrack stack; step/stack overflow bumps a
 // global counter and the host re-runs the column on CPU (exactness over
 // silent divergence).
+#include "hipdf.h"
 #include "hipdf_common.h"
 
 enum RxOp : int {

@@ -8,6 +8,7 @@
 // Used by: filter compaction, string gather offsets, join match offsets,
 // partition offsets. Reductions: wave shfl -> LDS -> one device atomic per
 // block (guide §6 G12).
+#include "hipdf.h"
 #include "hipdf_common.h"
 
 #define SCAN_ITEMS 8  // elements per thread

@@ -7,6 +7,7 @@
 // exclusive scan of counts (device-wide, see scan.hip; orchestrated from
 // python) -> scatter with intra-block prefix from wave ballots. Phase 1 and
 // phase 3 iterate rows in the same order so offsets line up.
+#include "hipdf.h"
 #include "hipdf_common.h"
 
 #define SEL_ITEMS 4  // rows per thread per block pass
@@ -111,14 +112,7 @@ __global__ void k_gather_validity(const uint64_t* __restrict__ in_valid,
 
 // fused whole-table gather for fixed-width columns: one launch gathers
 // every column (the index load and ballot amortize across columns)
-struct GatherCol {
-  int esize;
-  int in_has_valid;
-  const void* in;
-  const uint64_t* in_valid;
-  void* out;
-  uint64_t* out_valid;  // may be null
-};
+using GatherCol = HipdfGatherCol;
 
 __global__ void k_gather_table(const GatherCol* __restrict__ cols, int ncols,
                                const int32_t* __restrict__ idx,

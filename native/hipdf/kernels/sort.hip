@@ -20,8 +20,8 @@
 // and scan and copies keys and perm through, so the host's buffer ping-pong
 // never depends on device state. The per-kernel entries remain for callers
 // that drive single steps (range_key, tests).
+#include "hipdf.h"
 #include "hipdf_common.h"
-#include "sort_desc.h"
 #include "sort_keys.h"
 
 #define SORT_BLOCK 256
@@ -336,10 +336,6 @@ void hipdf_radix_scatter(const void* keys_in, const void* perm_in, int shift,
                      shift, (const int64_t*)offsets, nb, (uint64_t*)keys_out,
                      (int32_t*)perm_out, n, (const uint64_t*)nullptr);
 }
-
-void hipdf_exclusive_scan_i64_skip(const void*, void*, void*, int64_t,
-                                   const void*, int, hipStream_t);  // scan.hip
-void hipdf_iota_i32(void*, int64_t, hipStream_t);  // window.hip
 
 // The whole multi-key sort, enqueued on `stream` with no allocation and no
 // synchronise: for each key, least significant first, build the u64 keys

@@ -4,6 +4,7 @@
 // length/substring count codepoints, upper/lower transform ASCII bytes
 // (non-ASCII passes through; gated by incompatibleOps like the reference's
 // incompat ops).
+#include "hipdf.h"
 #include "hipdf_common.h"
 
 enum StrCmpOp : int { SC_EQ = 0, SC_NE, SC_LT, SC_LE, SC_GT, SC_GE };
@@ -285,11 +286,7 @@ __global__ void k_i64_to_str(const int64_t* __restrict__ vals,
 
 // concat_ws: join n string columns with a separator, skipping NULL
 // values (result is never null — all-null rows give ""). Two-pass.
-struct StrColDesc {
-  const int32_t* off;
-  const uint8_t* bytes;
-  const uint64_t* valid;
-};
+using StrColDesc = HipdfStrColDesc;
 
 __global__ void k_str_concat_ws(const StrColDesc* __restrict__ cols,
                                 int ncols, const uint8_t* __restrict__ sep,

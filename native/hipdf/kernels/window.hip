@@ -5,6 +5,7 @@
 //  - change flags: row differs from the previous row on the given keys
 //  - iota: row index column
 //  - double-typed device-wide scan blocks (running sums over f64)
+#include "hipdf.h"
 #include "hipdf_common.h"
 #include "keys.h"
 

@@ -10,6 +10,8 @@
 // host memory in the CPU test suite.
 #include <hip/hip_runtime.h>
 
+#include "hipdf.h"
+
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -98,9 +100,7 @@ void* g_slab = nullptr;
 // spilling could not help (tracked so free routes correctly)
 std::map<void*, size_t> g_overflow;
 size_t g_overflow_bytes = 0;
-// failure callback: returns nonzero if it freed memory and the alloc
-// should be retried (Python side: spill device->host)
-typedef int (*hipdf_failure_cb)(size_t needed, int retry);
+// failure callback (hipdf.h): nonzero = it freed memory, retry the alloc
 hipdf_failure_cb g_cb = nullptr;
 
 }  // namespace

@@ -1,9 +1,10 @@
 // Non-python consumer of the hipdf C ABI: links
-// against libhipdf.so and runs filter -> gather -> hash group-by on
-// device, verifying results on the host. Build:
+// against libhipdf.so and runs filter -> gather -> hash group-by, then a
+// two-key sort, on device, verifying results on the host. Build:
 //   hipcc -I native/hipdf/include c_api_test.cpp -L. -lhipdf -o c_api_test
 #include <hipdf.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -141,6 +142,62 @@ int main() {
       return 1;
     }
   }
+
+  // ---- multi-key sort through HipdfSortKey -----------------------------
+  // key 0: int32, 7 distinct values, ascending; key 1: int64 descending,
+  // row 0 null, NULLS LAST. Scratch sized as gpu_backend.py sizes it.
+  const int64_t NS = 1000;
+  std::vector<int32_t> sk0(NS);
+  std::vector<int64_t> sk1(NS);
+  std::vector<uint64_t> sv1((NS + 63) / 64, ~0ull);
+  for (int64_t i = 0; i < NS; ++i) {
+    sk0[i] = (int32_t)((i * 5 + 3) % 7);
+    sk1[i] = (i * 7919) % 101 - 50;  // repeats, so ties test stability
+  }
+  sv1[0] &= ~1ull;
+  int32_t* d_sk0 = dev(sk0);
+  int64_t* d_sk1 = dev(sk1);
+  uint64_t* d_sv1 = dev(sv1);
+  CHECK(d_sk0 && d_sk1 && d_sv1);
+  HipdfSortKey sort_keys[2] = {
+      {SORT_KEY_FIXED, HIPDF_I32, d_sk0, nullptr, nullptr, 0, 0, 0, 0},
+      {SORT_KEY_FIXED, HIPDF_I64, d_sk1, d_sv1, nullptr, 1, 1, 1, 0},
+  };
+  int64_t ncounts = 256 * sort_num_blocks(NS);
+  int64_t nscan = scan_scratch_elems(ncounts);
+  void *d_ka, *d_kb, *d_pa, *d_pb, *d_cnts, *d_scanned, *d_sscratch, *d_diff,
+      *d_perm;
+  HIP_OK(hipMalloc(&d_ka, NS * 8));
+  HIP_OK(hipMalloc(&d_kb, NS * 8));
+  HIP_OK(hipMalloc(&d_pa, NS * 4));
+  HIP_OK(hipMalloc(&d_pb, NS * 4));
+  HIP_OK(hipMalloc(&d_cnts, ncounts * 8));
+  HIP_OK(hipMalloc(&d_scanned, ncounts * 8));
+  HIP_OK(hipMalloc(&d_sscratch, nscan * 8));
+  HIP_OK(hipMalloc(&d_diff, 8));
+  HIP_OK(hipMalloc(&d_perm, NS * 4));
+  hipdf_sort_order(sort_keys, 2, NS, d_ka, d_kb, d_pa, d_pb, d_cnts,
+                   d_scanned, d_sscratch, d_diff, d_perm, s);
+  HIP_OK(hipDeviceSynchronize());
+  std::vector<int32_t> h_perm(NS), ref_perm(NS);
+  HIP_OK(hipMemcpy(h_perm.data(), d_perm, NS * 4, hipMemcpyDeviceToHost));
+  for (int64_t i = 0; i < NS; ++i) ref_perm[i] = (int32_t)i;
+  std::stable_sort(ref_perm.begin(), ref_perm.end(),
+                   [&](int32_t a, int32_t b) {
+                     if (sk0[a] != sk0[b]) return sk0[a] < sk0[b];
+                     bool null_a = a == 0, null_b = b == 0;  // row 0
+                     if (null_a != null_b) return null_b;    // nulls last
+                     if (null_a) return false;
+                     return sk1[a] > sk1[b];  // descending
+                   });
+  for (int64_t i = 0; i < NS; ++i) {
+    if (h_perm[i] != ref_perm[i]) {
+      fprintf(stderr, "sort perm[%lld]: got %d want %d\n", (long long)i,
+              h_perm[i], ref_perm[i]);
+      return 1;
+    }
+  }
+
   printf("C_API_OK filter=%lld/%lld groups=%d\n", (long long)n_sel,
          (long long)N, ngroups);
   return 0;

@@ -400,6 +400,7 @@ def concat_ws(sep: str, cols) -> Column:
     s = _stream()
     if n == 0:
         return _empty_col(DType.string())
+    # HipdfStrColDesc (see native/hipdf/include/hipdf.h)
     blob = b"".join(struct.pack("<qqq", c.offsets.data_ptr(),
                                 c.data.data_ptr(), _ptr(c.validity))
                     for c in cols)
@@ -1384,6 +1385,7 @@ def _gather_by_idx(batch: ColumnBatch, idx: torch.Tensor, n_out: int,
             need_valid = c.validity is not None or maybe_negative
             ov = _alloc_mask(n_out) if need_valid else None
             outs.append((ci, c, out, ov))
+            # HipdfGatherCol (see native/hipdf/include/hipdf.h)
             blobs.append(struct.pack(
                 "<iiqqqq", c.dtype.itemsize,
                 1 if c.validity is not None else 0, c.data.data_ptr(),
@@ -1589,8 +1591,9 @@ def reduce(op: str, col: Column):
 # ---------------------------------------------------------------------------
 
 def _key_desc(cols: List[Column]) -> torch.Tensor:
-    """Pack KeyCol structs (see native/hipdf/kernels/keys.h) into device mem:
-    {int type; int is_string; void* data; u64* valid; void* aux} = 32 B."""
+    """Pack HipdfKeyCol structs (see native/hipdf/include/hipdf.h) into
+    device mem: {int type; int is_string; void* data; u64* valid; void* aux}
+    = 32 B."""
     blobs = []
     for c in cols:
         if c.dtype.id is TypeId.STRING:
@@ -1756,6 +1759,7 @@ def group_by_aggregate(batch: ColumnBatch, key_idx: List[int],
                                   and not vc.dtype.is_floating))) else 0
         allocs.append((op, out_dtype, acc_is_double, acc, cnt,
                        skip_cnt))
+        # HipdfAggDesc (see native/hipdf/include/hipdf.h)
         blobs.append(struct.pack(
             "<iiiiqqqq", _GB[op], t, acc_is_double, skip_cnt,
             _ptr(vc.data if vc is not None else None),
@@ -1850,6 +1854,7 @@ def _try_dense_keys(keys, aggs, selp, n):
         strides[i] = acc
         acc *= ranges[i]
     s = _stream()
+    # HipdfDenseKey (see native/hipdf/include/hipdf.h)
     blob = b"".join(
         struct.pack("<iiqqqqq", _ht(k.dtype), 0, k.data.data_ptr(), 0,
                     mins[i], ranges[i], strides[i])
@@ -2192,7 +2197,7 @@ def join_gather_maps(left: ColumnBatch, right: ColumnBatch,
 # sort: stable LSD radix over order-preserving u64 keys (native/hipdf sort.hip)
 # ---------------------------------------------------------------------------
 
-# HipdfSortKind of native/hipdf/kernels/sort_desc.h
+# HipdfSortKind of native/hipdf/include/hipdf.h
 _SORT_KEY_FIXED, _SORT_KEY_STRING, _SORT_KEY_DECIMAL128 = 0, 1, 2
 
 
