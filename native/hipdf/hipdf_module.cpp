@@ -520,4 +520,7 @@ PYBIND11_MODULE(hipdf, m) {
   BIND(list_sort_block);
   BIND(list_distinct_flags);
   BIND(list_argminmax);
+  BIND(list_member_flags);
+  BIND(list_overlap);
+  BIND(list_union_map);
 }

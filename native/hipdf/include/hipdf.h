@@ -641,6 +641,39 @@ void hipdf_list_argminmax(int t, const void* data, const void* eoffs,
                           const void* cvalid, const void* offsets,
                           const void* rvalid, int w, int is_max, void* out,
                           int64_t n, hipStream_t stream);
+/* Two-list set operations: side a is probed against side b row by row; both
+ * are LISTs of n rows with the same element type t, each with its own child,
+ * validity and first offset. bperm is b's ascending, nulls-first sort
+ * permutation (hipdf_list_sort_*), or NULL when b has no elements.
+ * member: uint8[total], total = aoffsets[n] - aoffsets[0]; entry p is 1 when
+ * element aoffsets[0] + p of a equals an element of the same row of b (null
+ * equals null, NaN equals NaN, -0.0 equals 0.0) */
+void hipdf_list_member_flags(int t, const void* adata, const void* aeoffs,
+                             const void* acvalid, const void* aoffsets,
+                             const void* bdata, const void* beoffs,
+                             const void* bcvalid, const void* boffsets,
+                             const void* bperm, int64_t n, void* member,
+                             int64_t total, hipStream_t stream);
+/* arrays_overlap from a's member flags, w lanes (8/16/32/64) per row. out:
+ * uint8[n], 1 = a non-null element is shared. vout: validity words covering
+ * n rows, every word written whole; a row is NULL when either row validity
+ * (arvalid / brvalid, may be NULL) says so, or when nothing is shared, both
+ * rows are non-empty and either holds a null element */
+void hipdf_list_overlap(const void* member, const void* aoffsets,
+                        const void* acvalid, const void* arvalid,
+                        const void* boffsets, const void* bcvalid,
+                        const void* brvalid, const void* bperm, int w,
+                        void* out, void* vout, int64_t n,
+                        hipStream_t stream);
+/* array_union's gather map. ascan: int64[atotal + 1] exclusive scan of a's
+ * kept flags (last slot = kept count), bscan likewise. new_offs: int32[n+1];
+ * idx: int32[kept a + kept b] rows of concat(a.child, b.child), b's child
+ * starting at row bbase; result row r = a's kept elements, then b's */
+void hipdf_list_union_map(const void* ascan, const void* aoffsets,
+                          int64_t atotal, const void* bscan,
+                          const void* boffsets, int64_t btotal, int64_t n,
+                          int64_t bbase, void* new_offs, void* idx,
+                          hipStream_t stream);
 
 /* ---- device memory pool (pool.hip) ------------------------------------- */
 /* reserve `bytes` (or fraction of free memory if bytes==0) as the pool

@@ -1,6 +1,7 @@
 // Segmented operations inside the rows of a LIST column (reference analogue:
 // GpuSortArray / GpuArraySort / GpuArrayDistinct / GpuArrayMin / GpuArrayMax
-// in collectionOperations.scala, reached there through cudf segmented sort).
+// in collectionOperations.scala, reached there through cudf segmented sort),
+// and the two-list set operations built on the sorted order (further down).
 //
 // Inputs are always the LIST offsets (int32[n+1], offsets[0] need not be 0),
 // the child's values and the child's validity bitmask. The sort produces an
@@ -34,15 +35,25 @@
 template <typename T>
 struct FixedSrc {
   const T* data;
+  static FixedSrc of(const void* data, const void*) {
+    return FixedSrc{(const T*)data};
+  }
   __device__ __forceinline__ uint64_t key(int32_t i) const {
     return sort_key_of<T>(data[i]);
   }
   __device__ __forceinline__ int tie(int32_t, int32_t) const { return 0; }
+  __device__ __forceinline__ int tie(int32_t, const FixedSrc&,
+                                     int32_t) const {
+    return 0;
+  }
 };
 
 struct StrSrc {
   const int32_t* offs;
   const uint8_t* bytes;
+  static StrSrc of(const void* data, const void* eoffs) {
+    return StrSrc{(const int32_t*)eoffs, (const uint8_t*)data};
+  }
   __device__ __forceinline__ uint64_t key(int32_t i) const {
     int32_t a = offs[i], b = offs[i + 1];
     uint64_t k = 0;
@@ -60,6 +71,17 @@ struct StrSrc {
     int32_t m = lx < ly ? lx : ly;
     for (int32_t j = m < 8 ? m : 8; j < m; ++j) {
       uint8_t cx = bytes[ax + j], cy = bytes[ay + j];
+      if (cx != cy) return cx < cy ? -1 : 1;
+    }
+    return lx == ly ? 0 : (lx < ly ? -1 : 1);
+  }
+  // the same between element x here and element y of another child
+  __device__ int tie(int32_t x, const StrSrc& o, int32_t y) const {
+    int32_t ax = offs[x], ay = o.offs[y];
+    int32_t lx = offs[x + 1] - ax, ly = o.offs[y + 1] - ay;
+    int32_t m = lx < ly ? lx : ly;
+    for (int32_t j = m < 8 ? m : 8; j < m; ++j) {
+      uint8_t cx = bytes[ax + j], cy = o.bytes[ay + j];
       if (cx != cy) return cx < cy ? -1 : 1;
     }
     return lx == ly ? 0 : (lx < ly ? -1 : 1);
@@ -305,15 +327,169 @@ __global__ __launch_bounds__(HIPDF_BLOCK) void k_list_argminmax(
   }
 }
 
+// ---- two-list set operations ---------------------------------------------
+// array_union / array_intersect / array_except / arrays_overlap (reference
+// analogue: GpuArrayUnion, GpuArrayIntersect, GpuArrayExcept,
+// GpuArraysOverlap). Side a is probed against side b, row by row. The two
+// sides have their own children, validity masks and first offsets; b comes
+// with its ascending, nulls-first sorted permutation.
+
+// last row r in [0, n) with offsets[r] <= pos; needs n >= 1 and
+// offsets[0] <= pos < offsets[n]
+__device__ __forceinline__ int64_t row_of(const int32_t* __restrict__ offsets,
+                                          int64_t n, int32_t pos) {
+  int64_t lo = 0, hi = n;
+  while (hi - lo > 1) {
+    int64_t mid = (lo + hi) >> 1;
+    if (offsets[mid] <= pos) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// member[p] = 1 when element (aoffsets[0] + p) of a has an equal element in
+// the same row of b. A null element of a is a member exactly when b's sorted
+// row starts with a null; otherwise a lower-bound style binary search over
+// b's sorted row on (prefix key, byte tie-break), nulls of b sorting first.
+template <typename Src>
+__global__ void k_list_member_flags(Src a, const int32_t* __restrict__ aoffs,
+                                    const uint64_t* __restrict__ avalid,
+                                    Src b, const int32_t* __restrict__ boffs,
+                                    const uint64_t* __restrict__ bvalid,
+                                    const int32_t* __restrict__ bperm,
+                                    int64_t n, uint8_t* __restrict__ member,
+                                    int64_t total) {
+  int32_t aoff0 = aoffs[0], boff0 = boffs[0];
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total;
+       p += (int64_t)gridDim.x * blockDim.x) {
+    int32_t gi = aoff0 + (int32_t)p;
+    int64_t row = row_of(aoffs, n, gi);
+    // positions inside bperm, rebased by b's own first offset
+    int32_t lo = boffs[row] - boff0, hi = boffs[row + 1] - boff0;
+    bool hit = false;
+    if (lo < hi) {
+      if (!valid_bit(avalid, gi)) {
+        hit = !valid_bit(bvalid, bperm[lo]);
+      } else {
+        uint64_t ka = a.key(gi);
+        while (lo < hi) {
+          int32_t mid = lo + ((hi - lo) >> 1);
+          int32_t gj = bperm[mid];
+          int c;  // order of b's element against the probe
+          if (!valid_bit(bvalid, gj)) {
+            c = -1;
+          } else {
+            uint64_t kb = b.key(gj);
+            c = kb < ka ? -1 : (kb > ka ? 1 : b.tie(gj, a, gi));
+          }
+          if (c == 0) { hit = true; break; }
+          if (c < 0) lo = mid + 1; else hi = mid;
+        }
+      }
+    }
+    member[p] = hit ? 1 : 0;
+  }
+}
+
+// arrays_overlap per row from a's member flags: 1 when a non-null element of
+// a is a member; else NULL when both rows are non-empty and either holds a
+// null (b's is its first sorted element); else 0. A row that is null on
+// either side is NULL. One wave owns a stripe of 64 rows, W lanes per row and
+// WAVE / W rows at a time, so it writes the stripe's validity word whole.
+template <int W>
+__global__ __launch_bounds__(HIPDF_BLOCK) void k_list_overlap(
+    const uint8_t* __restrict__ member, const int32_t* __restrict__ aoffs,
+    const uint64_t* __restrict__ avalid, const uint64_t* __restrict__ arvalid,
+    const int32_t* __restrict__ boffs, const uint64_t* __restrict__ bvalid,
+    const uint64_t* __restrict__ brvalid, const int32_t* __restrict__ bperm,
+    uint8_t* __restrict__ out, uint64_t* __restrict__ vout, int64_t n) {
+  constexpr int L = WAVE / W;  // rows per step
+  int lane = lane_id();
+  int sub = lane / W, sl = lane & (W - 1);
+  int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  int64_t nwaves = (int64_t)gridDim.x * blockDim.x / WAVE;
+  int64_t nstripes = (n + WAVE - 1) / WAVE;
+  int32_t aoff0 = aoffs[0], boff0 = boffs[0];
+  // loop bounds are wave-uniform: every lane reaches every shuffle / ballot
+  for (int64_t stripe = wave; stripe < nstripes; stripe += nwaves) {
+    uint64_t word = 0;
+    for (int step = 0; step < W; ++step) {
+      int64_t row = stripe * WAVE + step * L + sub;
+      bool rv = row < n && valid_bit(arvalid, row) && valid_bit(brvalid, row);
+      int32_t astart = 0, alen = 0, bstart = 0, blen = 0;
+      if (rv) {
+        astart = aoffs[row];
+        alen = aoffs[row + 1] - astart;
+        bstart = boffs[row];
+        blen = boffs[row + 1] - bstart;
+      }
+      int hit = 0, anull = 0;
+      for (int32_t i = sl; i < alen; i += W) {
+        int32_t gi = astart + i;
+        if (valid_bit(avalid, gi)) hit |= member[gi - aoff0];
+        else anull = 1;
+      }
+      int st = hit | (anull << 1);
+#pragma unroll
+      for (int j = W >> 1; j > 0; j >>= 1) st |= __shfl_xor(st, j, W);
+      bool bnull = blen > 0 && !valid_bit(bvalid, bperm[bstart - boff0]);
+      bool any = (st & 1) != 0;
+      bool unknown = !any && alen > 0 && blen > 0 && ((st & 2) || bnull);
+      bool valid = rv && !unknown;
+      uint64_t bal = __ballot(valid && sl == 0);  // bit sub * W = row's bit
+#pragma unroll
+      for (int g = 0; g < L; ++g)
+        word |= ((bal >> (g * W)) & 1ull) << (step * L + g);
+      if (sl == 0 && row < n) out[row] = (valid && any) ? 1 : 0;
+    }
+    if (lane == 0) vout[stripe] = word;
+  }
+}
+
+// array_union's layout: row r of the result is a's kept elements followed by
+// b's. ascan / bscan are exclusive scans of the kept flags with one extra
+// slot for the total. One flat index space covers the n + 1 new offsets, a's
+// elements and b's elements; idx points into concat(a.child, b.child), where
+// b's child starts at row bbase.
+__global__ void k_list_union_map(const int64_t* __restrict__ ascan,
+                                 const int32_t* __restrict__ aoffs,
+                                 int64_t atotal,
+                                 const int64_t* __restrict__ bscan,
+                                 const int32_t* __restrict__ boffs,
+                                 int64_t btotal, int64_t n, int32_t bbase,
+                                 int32_t* __restrict__ new_offs,
+                                 int32_t* __restrict__ idx) {
+  int32_t aoff0 = aoffs[0], boff0 = boffs[0];
+  int64_t work = n + 1 + atotal + btotal;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < work;
+       t += (int64_t)gridDim.x * blockDim.x) {
+    if (t <= n) {
+      new_offs[t] = (int32_t)(ascan[aoffs[t] - aoff0] +
+                              bscan[boffs[t] - boff0]);
+    } else if (t < n + 1 + atotal) {
+      int64_t p = t - (n + 1);
+      if (ascan[p + 1] == ascan[p]) continue;
+      int32_t gi = aoff0 + (int32_t)p;
+      int64_t row = row_of(aoffs, n, gi);
+      idx[ascan[p] + bscan[boffs[row] - boff0]] = gi;
+    } else {
+      int64_t q = t - (n + 1 + atotal);
+      if (bscan[q + 1] == bscan[q]) continue;
+      int32_t gj = boff0 + (int32_t)q;
+      int64_t row = row_of(boffs, n, gj);
+      idx[bscan[q] + ascan[aoffs[row + 1] - aoff0]] = bbase + gj;
+    }
+  }
+}
+
 // ---- host side -----------------------------------------------------------
 
 template <typename F>
 static inline void dispatch_src(int t, const void* data, const void* eoffs,
                                 F&& f) {
   if (t == LT_STR) {
-    f(StrSrc{(const int32_t*)eoffs, (const uint8_t*)data});
+    f(StrSrc::of(data, eoffs));
   } else {
-    dispatch_type(t, [&]<typename T>() { f(FixedSrc<T>{(const T*)data}); });
+    dispatch_type(t, [&]<typename T>() { f(FixedSrc<T>::of(data, eoffs)); });
   }
 }
 
@@ -402,6 +578,56 @@ void hipdf_list_argminmax(int t, const void* data, const void* eoffs,
                          (const uint64_t*)rvalid, is_max, (int32_t*)out, n);
     });
   });
+}
+
+void hipdf_list_member_flags(int t, const void* adata, const void* aeoffs,
+                             const void* acvalid, const void* aoffsets,
+                             const void* bdata, const void* beoffs,
+                             const void* bcvalid, const void* boffsets,
+                             const void* bperm, int64_t n, void* member,
+                             int64_t total, hipStream_t stream) {
+  if (n <= 0 || total <= 0) return;
+  dispatch_src(t, adata, aeoffs, [&](auto a) {
+    using Src = decltype(a);
+    hipLaunchKernelGGL((k_list_member_flags<Src>), flat_grid(total),
+                       dim3(HIPDF_BLOCK), 0, stream, a,
+                       (const int32_t*)aoffsets, (const uint64_t*)acvalid,
+                       Src::of(bdata, beoffs), (const int32_t*)boffsets,
+                       (const uint64_t*)bcvalid, (const int32_t*)bperm, n,
+                       (uint8_t*)member, total);
+  });
+}
+
+void hipdf_list_overlap(const void* member, const void* aoffsets,
+                        const void* acvalid, const void* arvalid,
+                        const void* boffsets, const void* bcvalid,
+                        const void* brvalid, const void* bperm, int w,
+                        void* out, void* vout, int64_t n,
+                        hipStream_t stream) {
+  if (n <= 0) return;
+  int64_t waves = (n + WAVE - 1) / WAVE;  // one wave per 64-row stripe
+  dispatch_width(w, [&]<int W>() {
+    hipLaunchKernelGGL((k_list_overlap<W>), flat_grid(waves * WAVE),
+                       dim3(HIPDF_BLOCK), 0, stream, (const uint8_t*)member,
+                       (const int32_t*)aoffsets, (const uint64_t*)acvalid,
+                       (const uint64_t*)arvalid, (const int32_t*)boffsets,
+                       (const uint64_t*)bcvalid, (const uint64_t*)brvalid,
+                       (const int32_t*)bperm, (uint8_t*)out, (uint64_t*)vout,
+                       n);
+  });
+}
+
+void hipdf_list_union_map(const void* ascan, const void* aoffsets,
+                          int64_t atotal, const void* bscan,
+                          const void* boffsets, int64_t btotal, int64_t n,
+                          int64_t bbase, void* new_offs, void* idx,
+                          hipStream_t stream) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_list_union_map, flat_grid(n + 1 + atotal + btotal),
+                     dim3(HIPDF_BLOCK), 0, stream, (const int64_t*)ascan,
+                     (const int32_t*)aoffsets, atotal, (const int64_t*)bscan,
+                     (const int32_t*)boffsets, btotal, n, (int32_t)bbase,
+                     (int32_t*)new_offs, (int32_t*)idx);
 }
 
 }  // extern "C"

@@ -187,6 +187,27 @@ class Expression:
     def array_max(self) -> "ArrayMax":
         return ArrayMax(self)
 
+    def array_union(self, other: "Expression") -> "ArrayUnion":
+        """Distinct elements of this LIST value, then those of `other` not
+        already present (Spark array_union); NULL when either is."""
+        return ArrayUnion(self, other)
+
+    def array_intersect(self, other: "Expression") -> "ArrayIntersect":
+        """Distinct elements of this LIST value that also occur in `other`,
+        in this value's order (Spark array_intersect)."""
+        return ArrayIntersect(self, other)
+
+    def array_except(self, other: "Expression") -> "ArrayExcept":
+        """Distinct elements of this LIST value that do not occur in
+        `other` (Spark array_except)."""
+        return ArrayExcept(self, other)
+
+    def arrays_overlap(self, other: "Expression") -> "ArraysOverlap":
+        """True when the two LIST values share a non-null element, NULL
+        when they share none, both are non-empty and either holds a null,
+        else false (Spark arrays_overlap)."""
+        return ArraysOverlap(self, other)
+
     def regexp_extract(self, pattern: str, group: int = 1) -> "RegexpExtract":
         return RegexpExtract(self, pattern, group)
 
@@ -834,6 +855,72 @@ class ArrayMax(Expression):
 
     def __str__(self):
         return f"array_max({self.child})"
+
+
+class _ArraySetOp(Expression):
+    """Two LIST operands of one element type; element equality is
+    array_distinct's (NaN equals NaN, -0.0 equals 0.0, null equals null).
+    A row is NULL when either operand row is."""
+
+    fn = ""
+
+    def __init__(self, left: Expression, right: Expression):
+        self.left = left
+        self.right = right
+
+    @property
+    def children(self):
+        return (self.left, self.right)
+
+    def _list_dtype(self, schema: Schema) -> DType:
+        lt, rt = self.left.dtype(schema), self.right.dtype(schema)
+        if lt.id is not TypeId.LIST or rt.id is not TypeId.LIST or lt != rt:
+            raise TypeError(f"{self.fn} needs two arrays of the same element "
+                            f"type, got {lt} and {rt}")
+        return lt
+
+    def dtype(self, schema: Schema) -> DType:
+        return self._list_dtype(schema)
+
+    def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
+        self._list_dtype(schema)
+        return getattr(ops, self.fn)(self.left.eval(batch, schema),
+                                     self.right.eval(batch, schema))
+
+    def __str__(self):
+        return f"{self.fn}({self.left}, {self.right})"
+
+
+class ArrayUnion(_ArraySetOp):
+    """array_union(a, b): distinct(a) then the distinct elements of b not
+    in a, first-occurrence order (GpuArrayUnion analogue)."""
+
+    fn = "array_union"
+
+
+class ArrayIntersect(_ArraySetOp):
+    """array_intersect(a, b): distinct elements of a that occur in b, a's
+    order and bit patterns (GpuArrayIntersect analogue)."""
+
+    fn = "array_intersect"
+
+
+class ArrayExcept(_ArraySetOp):
+    """array_except(a, b): distinct elements of a that do not occur in b
+    (GpuArrayExcept analogue)."""
+
+    fn = "array_except"
+
+
+class ArraysOverlap(_ArraySetOp):
+    """arrays_overlap(a, b): true / NULL / false, see
+    Expression.arrays_overlap (GpuArraysOverlap analogue)."""
+
+    fn = "arrays_overlap"
+
+    def dtype(self, schema: Schema) -> DType:
+        self._list_dtype(schema)
+        return DType.bool_()
 
 
 class HostStringFn(Expression):

@@ -86,6 +86,28 @@ def array_max(col: Column) -> Column:
     return backend_for(col).array_max(col)
 
 
+def array_union(a: Column, b: Column) -> Column:
+    """Distinct elements of a, then those of b not in a, first-occurrence
+    order; NULL when either row is (GpuArrayUnion analogue)."""
+    return backend_for(a, b).array_union(a, b)
+
+
+def array_intersect(a: Column, b: Column) -> Column:
+    """Distinct elements of a that occur in b, a's order (GpuArrayIntersect)."""
+    return backend_for(a, b).array_intersect(a, b)
+
+
+def array_except(a: Column, b: Column) -> Column:
+    """Distinct elements of a that do not occur in b (GpuArrayExcept)."""
+    return backend_for(a, b).array_except(a, b)
+
+
+def arrays_overlap(a: Column, b: Column) -> Column:
+    """True on a shared non-null element, else NULL when both are non-empty
+    and either holds a null, else false (GpuArraysOverlap)."""
+    return backend_for(a, b).arrays_overlap(a, b)
+
+
 def map_keys(col: Column) -> Column:
     """MAP -> LIST<key>: shares the offsets and the entry key child
     buffer (zero-copy, reference GpuMapKeys)."""

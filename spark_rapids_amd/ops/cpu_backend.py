@@ -740,6 +740,86 @@ def array_max(col: Column) -> Column:
     return _array_extreme(col, max)
 
 
+def _array_set_key(x):
+    """Equality key of one element, null included (a null equals a null)."""
+    return None if x is None else _array_elem_key(x)
+
+
+def _array_pair_rows(a: Column, b: Column):
+    if a.dtype.id is not TypeId.LIST or a.dtype != b.dtype:
+        raise TypeError("array set operations need two arrays of one "
+                        f"element type, got {a.dtype} and {b.dtype}")
+    return zip(a.to_pylist(), b.to_pylist())
+
+
+def _array_filter_by_member(a: Column, b: Column, negate: bool) -> Column:
+    out = []
+    for va, vb in _array_pair_rows(a, b):
+        if va is None or vb is None:
+            out.append(None)
+            continue
+        other = {_array_set_key(y) for y in vb}
+        seen = set()
+        kept = []
+        for x in va:
+            k = _array_set_key(x)
+            if k not in seen:
+                seen.add(k)
+                if (k in other) != negate:
+                    kept.append(x)
+        out.append(kept)
+    return Column.from_pylist(out, a.dtype)
+
+
+def array_intersect(a: Column, b: Column) -> Column:
+    """First occurrences of a's elements that occur in b, in a's order and
+    with a's bit patterns; a null survives only if both hold one."""
+    return _array_filter_by_member(a, b, False)
+
+
+def array_except(a: Column, b: Column) -> Column:
+    """First occurrences of a's elements that do not occur in b."""
+    return _array_filter_by_member(a, b, True)
+
+
+def array_union(a: Column, b: Column) -> Column:
+    """Distinct elements of a, then the distinct elements of b not in a,
+    each in first-occurrence order; at most one null."""
+    out = []
+    for va, vb in _array_pair_rows(a, b):
+        if va is None or vb is None:
+            out.append(None)
+            continue
+        seen = set()
+        kept = []
+        for x in va + vb:
+            k = _array_set_key(x)
+            if k not in seen:
+                seen.add(k)
+                kept.append(x)
+        out.append(kept)
+    return Column.from_pylist(out, a.dtype)
+
+
+def arrays_overlap(a: Column, b: Column) -> Column:
+    """True if a non-null element occurs in both; else NULL if both are
+    non-empty and either holds a null; else false. NULL for a null row."""
+    out = []
+    for va, vb in _array_pair_rows(a, b):
+        if va is None or vb is None:
+            out.append(None)
+            continue
+        ka = {_array_elem_key(x) for x in va if x is not None}
+        kb = {_array_elem_key(y) for y in vb if y is not None}
+        if ka & kb:
+            out.append(True)
+        elif va and vb and any(x is None for x in va + vb):
+            out.append(None)
+        else:
+            out.append(False)
+    return Column.from_pylist(out, DType.bool_())
+
+
 def map_get(col: Column, key) -> Column:
     out = []
     for v in col.to_pylist():  # dicts (last-win on duplicate keys)

@@ -909,15 +909,41 @@ def array_distinct(col: Column) -> Column:
     if total == 0:
         return _list_with_child(col, _list_rebased_offsets(col, off0),
                                 _empty_col(elem.dtype))
+    keep = _list_distinct_flags(col, perm, total)
+    new_offs, child = _list_compact(col, keep, off0, total)
+    return _list_with_child(col, new_offs, child)
+
+
+def _list_distinct_flags(col: Column, perm: torch.Tensor,
+                         total: int) -> torch.Tensor:
+    """uint8[total], 1 at the first occurrence of each value of its list;
+    `perm` is the ascending nulls-first `_list_sort_perm` (total > 0)."""
+    elem = col.child
     t, dp, eo = _list_elem_args(elem)
     keep = torch.empty(total, dtype=torch.uint8, device="cuda")
     ext.list_distinct_flags(t, dp, eo, _ptr(elem.validity),
-                            col.offsets.data_ptr(), n, perm.data_ptr(),
-                            keep.data_ptr(), total, s)
-    # kept-before counts at every element, one extra slot for the total
+                            col.offsets.data_ptr(), col.size,
+                            perm.data_ptr(), keep.data_ptr(), total,
+                            _stream())
+    return keep
+
+
+def _list_keep_scan(keep: Optional[torch.Tensor], total: int):
+    """(exclusive scan of the uint8 keep flags as int64[total + 1], kept
+    count): kept-before counts at every element, one extra slot for the
+    total."""
     keep64 = torch.zeros(total + 1, dtype=torch.int64, device="cuda")
-    ext.cast(0, 4, keep.data_ptr(), keep64.data_ptr(), total, s)
-    scanned, nkept = _exclusive_scan_i64(keep64)
+    if total:
+        ext.cast(0, 4, keep.data_ptr(), keep64.data_ptr(), total, _stream())
+    return _exclusive_scan_i64(keep64)
+
+
+def _list_compact(col: Column, keep: torch.Tensor, off0: int, total: int):
+    """Drop the elements whose uint8 keep flag (one per element from
+    `off0`, total > 0) is 0, order kept: (new int32 offsets, new child)."""
+    n = col.size
+    s = _stream()
+    scanned, nkept = _list_keep_scan(keep, total)
     rebased = _list_rebased_offsets(col, off0)
     offs64 = torch.empty(n + 1, dtype=torch.int64, device="cuda")
     ext.gather_fixed(8, scanned.data_ptr(), rebased.data_ptr(),
@@ -930,8 +956,139 @@ def array_distinct(col: Column) -> Column:
         sel = binary_op_scalar(
             "add", Column(DType.int32(), nkept, sel, None, null_count=0),
             off0, DType.int32()).data
-    child = _gather_col(elem, sel, nkept, maybe_negative=False)
-    return _list_with_child(col, new_offs, child)
+    child = _gather_col(col.child, sel, nkept, maybe_negative=False)
+    return new_offs, child
+
+
+# two-list set operations: a is probed against b's sorted rows
+
+def _list_pair_check(a: Column, b: Column) -> None:
+    if a.dtype.id is not TypeId.LIST or a.dtype != b.dtype:
+        raise TypeError("array set operations need two arrays of one "
+                        f"element type, got {a.dtype} and {b.dtype}")
+    if a.size != b.size:
+        raise ValueError(f"array operands of {a.size} and {b.size} rows")
+
+
+def _list_pair_validity(a: Column, b: Column):
+    v = _and_masks(a.validity, b.validity)
+    return v, (None if v is not None else 0)
+
+
+def _list_member_flags(a: Column, atotal: int, b: Column,
+                       bperm: Optional[torch.Tensor]) -> torch.Tensor:
+    """uint8[atotal], 1 where the element of `a` has an equal element in
+    the same row of `b`; `bperm` is b's ascending nulls-first
+    `_list_sort_perm` (None when b has no elements)."""
+    t, adp, aeo = _list_elem_args(a.child)
+    _, bdp, beo = _list_elem_args(b.child)
+    member = torch.empty(atotal, dtype=torch.uint8, device="cuda")
+    ext.list_member_flags(t, adp, aeo, _ptr(a.child.validity),
+                          a.offsets.data_ptr(), bdp, beo,
+                          _ptr(b.child.validity), b.offsets.data_ptr(),
+                          _ptr(bperm), a.size, member.data_ptr(), atotal,
+                          _stream())
+    return member
+
+
+def _flag_col(flags: torch.Tensor) -> Column:
+    return Column(DType.bool_(), flags.numel(), flags, None, null_count=0)
+
+
+def _array_filter_by_member(a: Column, b: Column, negate: bool) -> Column:
+    """distinct(a) AND member (array_intersect), or AND NOT member
+    (array_except), compacted in a's order."""
+    _list_pair_check(a, b)
+    n = a.size
+    if n == 0:
+        return Column.from_pylist([], a.dtype).cuda()
+    v, nc = _list_pair_validity(a, b)
+    aperm, aoff0, atotal = _list_sort_perm(a, True, True)
+    if atotal == 0:
+        new_offs, child = _list_rebased_offsets(a, aoff0), \
+            _empty_col(a.child.dtype)
+    else:
+        bperm, _, _ = _list_sort_perm(b, True, True)
+        member = _flag_col(_list_member_flags(a, atotal, b, bperm))
+        if negate:
+            member = unary_op("not", member, DType.bool_())
+        keep = binary_op("and", _flag_col(_list_distinct_flags(a, aperm,
+                                                               atotal)),
+                         member, DType.bool_()).data
+        new_offs, child = _list_compact(a, keep, aoff0, atotal)
+    return Column(a.dtype, n, torch.zeros(0, dtype=torch.uint8, device="cuda"),
+                  v, new_offs, nc, child)
+
+
+def array_intersect(a: Column, b: Column) -> Column:
+    """First occurrences of a's elements that occur in b's row, a's order
+    and bit patterns."""
+    return _array_filter_by_member(a, b, False)
+
+
+def array_except(a: Column, b: Column) -> Column:
+    """First occurrences of a's elements that do not occur in b's row."""
+    return _array_filter_by_member(a, b, True)
+
+
+def array_union(a: Column, b: Column) -> Column:
+    """distinct(a) followed by distinct(b) AND NOT member-of-a, per row:
+    one gather map over concat(a.child, b.child) (list_union_map)."""
+    _list_pair_check(a, b)
+    n = a.size
+    s = _stream()
+    if n == 0:
+        return Column.from_pylist([], a.dtype).cuda()
+    v, nc = _list_pair_validity(a, b)
+    aperm, _, atotal = _list_sort_perm(a, True, True)
+    bperm, _, btotal = _list_sort_perm(b, True, True)
+    akeep = _list_distinct_flags(a, aperm, atotal) if atotal else None
+    bkeep = None
+    if btotal:
+        bkeep = _list_distinct_flags(b, bperm, btotal)
+        if atotal:
+            fresh = unary_op("not", _flag_col(
+                _list_member_flags(b, btotal, a, aperm)), DType.bool_())
+            bkeep = binary_op("and", _flag_col(bkeep), fresh,
+                              DType.bool_()).data
+    ascan, na = _list_keep_scan(akeep, atotal)
+    bscan, nb = _list_keep_scan(bkeep, btotal)
+    nkept = na + nb
+    if nkept > 2 ** 31 - 1:
+        raise OverflowError("array_union result exceeds int32 offsets")
+    new_offs = torch.empty(n + 1, dtype=torch.int32, device="cuda")
+    idx = torch.empty(max(nkept, 1), dtype=torch.int32, device="cuda")[:nkept]
+    ext.list_union_map(ascan.data_ptr(), a.offsets.data_ptr(), atotal,
+                       bscan.data_ptr(), b.offsets.data_ptr(), btotal, n,
+                       a.child.size, new_offs.data_ptr(), idx.data_ptr(), s)
+    if nkept:
+        both = concat_batches([ColumnBatch([a.child], a.child.size),
+                               ColumnBatch([b.child], b.child.size)])
+        child = _gather_col(both.columns[0], idx, nkept, maybe_negative=False)
+    else:
+        child = _empty_col(a.child.dtype)
+    return Column(a.dtype, n, torch.zeros(0, dtype=torch.uint8, device="cuda"),
+                  v, new_offs, nc, child)
+
+
+def arrays_overlap(a: Column, b: Column) -> Column:
+    """True when a non-null element is shared, else NULL when both rows are
+    non-empty and either holds a null, else false (list_overlap)."""
+    _list_pair_check(a, b)
+    n = a.size
+    if n == 0:
+        return _empty_col(DType.bool_())
+    aoff0, atotal, _, amax = _list_bounds(a)
+    bperm, _, btotal = _list_sort_perm(b, True, True)
+    member = _list_member_flags(a, atotal, b, bperm) if atotal else None
+    out = torch.empty(n, dtype=torch.uint8, device="cuda")
+    ov = _alloc_mask(n)
+    ext.list_overlap(_ptr(member), a.offsets.data_ptr(),
+                     _ptr(a.child.validity), _ptr(a.validity),
+                     b.offsets.data_ptr(), _ptr(b.child.validity),
+                     _ptr(b.validity), _ptr(bperm), _list_group_width(amax),
+                     out.data_ptr(), ov.data_ptr(), n, _stream())
+    return Column(DType.bool_(), n, out, ov, null_count=None)
 
 
 def _array_extreme(col: Column, is_max: bool) -> Column:

@@ -64,7 +64,13 @@ _GPU_STRING_UNARY = {"length", "upper", "lower", "trim", "ltrim",
 
 _ARRAY_FN_NAMES = {"SortArray": "sort_array", "ArraySort": "array_sort",
                    "ArrayDistinct": "array_distinct",
-                   "ArrayMin": "array_min", "ArrayMax": "array_max"}
+                   "ArrayMin": "array_min", "ArrayMax": "array_max",
+                   "ArrayUnion": "array_union",
+                   "ArrayIntersect": "array_intersect",
+                   "ArrayExcept": "array_except",
+                   "ArraysOverlap": "arrays_overlap"}
+_ARRAY_SET_OPS = ("ArrayUnion", "ArrayIntersect", "ArrayExcept",
+                  "ArraysOverlap")
 
 
 class TagReason:
@@ -159,11 +165,15 @@ class Tagger:
             et = e.child.dtype(schema).children[0]
             if et.is_nested:
                 out.append("array_contains over nested elements on CPU")
-        elif type(e).__name__ in ("SortArray", "ArraySort", "ArrayDistinct",
-                                  "ArrayMin", "ArrayMax"):
-            # segmented sort / distinct / arg-min-max kernels (lists.hip)
-            # cover fixed-width (<= 64 bit) and string elements
-            cdt = e.child.dtype(schema)
+        elif type(e).__name__ in _ARRAY_FN_NAMES:
+            # segmented sort / distinct / arg-min-max / membership kernels
+            # (lists.hip) cover fixed-width (<= 64 bit) and string elements;
+            # the two-operand ones check in dtype() that both sides agree
+            if type(e).__name__ in _ARRAY_SET_OPS:
+                e.dtype(schema)
+                cdt = e.left.dtype(schema)
+            else:
+                cdt = e.child.dtype(schema)
             fn = _ARRAY_FN_NAMES[type(e).__name__]
             if cdt.id is not TypeId.LIST:
                 out.append(f"{fn} needs an array input, got {cdt}")

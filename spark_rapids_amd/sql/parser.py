@@ -738,6 +738,17 @@ class Parser:
                    "array_min": _ex.ArrayMin,
                    "array_max": _ex.ArrayMax}[name]
             return cls(args[0])
+        if name in ("array_union", "array_intersect", "array_except",
+                    "arrays_overlap"):
+            from ..expr import expressions as _ex
+
+            if len(args) != 2:
+                raise ValueError(f"{name} takes two arguments")
+            cls = {"array_union": _ex.ArrayUnion,
+                   "array_intersect": _ex.ArrayIntersect,
+                   "array_except": _ex.ArrayExcept,
+                   "arrays_overlap": _ex.ArraysOverlap}[name]
+            return cls(args[0], args[1])
         if name in ("map_keys", "map_values", "map_entries"):
             from ..expr.expressions import MapView
 

@@ -191,6 +191,16 @@ _EXPR_ROWS = [
     ("ArrayMin", "array_min", "GPU",
      "segmented arg-min, nulls skipped, NaN greatest"),
     ("ArrayMax", "array_max", "GPU", "segmented arg-max"),
+    ("ArrayUnion", "array_union / col.array_union(other)", "GPU",
+     "distinct(a) then b's new elements, one gather map; same element "
+     "type on both sides; decimal128/nested elements CPU"),
+    ("ArrayIntersect", "array_intersect", "GPU",
+     "binary search in the other row's sorted order (lists.hip); a's "
+     "order and bit patterns"),
+    ("ArrayExcept", "array_except", "GPU",
+     "distinct(a) without b's elements"),
+    ("ArraysOverlap", "arrays_overlap", "GPU",
+     "true / NULL (a null and no shared element) / false"),
     ("CreateArray", "from_pylist lists", "CPU", "construction host-side"),
     # misc
     ("Rand", "SampleHash deterministic draw", "GPU", "sample() lowering"),
