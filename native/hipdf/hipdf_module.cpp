@@ -523,4 +523,6 @@ PYBIND11_MODULE(hipdf, m) {
   BIND(list_member_flags);
   BIND(list_overlap);
   BIND(list_union_map);
+  BIND(list_elem_rows);
+  BIND(list_bool_reduce);
 }

@@ -674,6 +674,22 @@ void hipdf_list_union_map(const void* ascan, const void* aoffsets,
                           const void* boffsets, int64_t btotal, int64_t n,
                           int64_t bbase, void* new_offs, void* idx,
                           hipStream_t stream);
+/* Element to row map of a LIST of n rows, total = offsets[n] - offsets[0]
+ * elements, one thread per element. rowid: int32[total], the row that owns
+ * element offsets[0] + p; pos: int32[total], its 0-based place in that row,
+ * or NULL when not wanted. Both are indexed from 0 */
+void hipdf_list_elem_rows(const void* offsets, int64_t n, void* rowid,
+                          void* pos, int64_t total, hipStream_t stream);
+/* exists (mode 0) / forall (mode 1) over pred, a BOOL column with one entry
+ * per element from offsets[0] (pvalid may be NULL), w lanes (8/16/32/64) per
+ * row. out: uint8[n]; vout: validity words covering n rows, every word
+ * written whole. exists: 1 when a predicate is true, else NULL when one is
+ * null, else 0. forall: 0 when a predicate is false, else NULL when one is
+ * null, else 1. A row that rvalid (may be NULL) marks null is NULL */
+void hipdf_list_bool_reduce(const void* pred, const void* pvalid,
+                            const void* offsets, const void* rvalid, int w,
+                            int mode, void* out, void* vout, int64_t n,
+                            hipStream_t stream);
 
 /* ---- device memory pool (pool.hip) ------------------------------------- */
 /* reserve `bytes` (or fraction of free memory if bytes==0) as the pool

@@ -1,7 +1,8 @@
 // Segmented operations inside the rows of a LIST column (reference analogue:
 // GpuSortArray / GpuArraySort / GpuArrayDistinct / GpuArrayMin / GpuArrayMax
 // in collectionOperations.scala, reached there through cudf segmented sort),
-// and the two-list set operations built on the sorted order (further down).
+// the two-list set operations built on the sorted order, and what the
+// higher-order functions need around a lambda body (both further down).
 //
 // Inputs are always the LIST offsets (int32[n+1], offsets[0] need not be 0),
 // the child's values and the child's validity bitmask. The sort produces an
@@ -481,6 +482,82 @@ __global__ void k_list_union_map(const int64_t* __restrict__ ascan,
   }
 }
 
+// ---- higher-order functions ----------------------------------------------
+// transform / filter / exists / forall evaluate a lambda body as ordinary
+// column kernels over the flattened child (reference analogue:
+// GpuArrayTransform, GpuArrayFilter, GpuArrayExists in
+// higherOrderFunctions.scala). What they need from here is the element to
+// row map, for outer columns and the position variable, and the per-row
+// three-valued reduction of the predicate column.
+
+// rowid[p] = row owning element (offsets[0] + p); pos[p] = its 0-based place
+// in that row (pos may be null). One thread per element: short rows keep
+// every lane busy, and both outputs are indexed from 0.
+__global__ void k_list_elem_rows(const int32_t* __restrict__ offsets,
+                                 int64_t n, int32_t* __restrict__ rowid,
+                                 int32_t* __restrict__ pos, int64_t total) {
+  int32_t off0 = offsets[0];
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total;
+       p += (int64_t)gridDim.x * blockDim.x) {
+    int32_t gi = off0 + (int32_t)p;
+    int64_t row = row_of(offsets, n, gi);
+    rowid[p] = (int32_t)row;
+    if (pos) pos[p] = gi - offsets[row];
+  }
+}
+
+// exists (decide = 1) / forall (decide = 0) per row over a predicate column
+// that has one entry per element from offsets[0]: the row is `decide` when a
+// non-null predicate equals it, else NULL when a predicate is null, else
+// !decide (so an empty row is false for exists, true for forall). A null row
+// is NULL whatever range it owns. Stripes, W and the word write are
+// k_list_overlap's; rows longer than W are covered by the stride.
+template <int W>
+__global__ __launch_bounds__(HIPDF_BLOCK) void k_list_bool_reduce(
+    const uint8_t* __restrict__ pred, const uint64_t* __restrict__ pvalid,
+    const int32_t* __restrict__ offsets, const uint64_t* __restrict__ rvalid,
+    int decide, uint8_t* __restrict__ out, uint64_t* __restrict__ vout,
+    int64_t n) {
+  constexpr int L = WAVE / W;  // rows per step
+  int lane = lane_id();
+  int sub = lane / W, sl = lane & (W - 1);
+  int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  int64_t nwaves = (int64_t)gridDim.x * blockDim.x / WAVE;
+  int64_t nstripes = (n + WAVE - 1) / WAVE;
+  int32_t off0 = offsets[0];
+  // loop bounds are wave-uniform: every lane reaches every shuffle / ballot
+  for (int64_t stripe = wave; stripe < nstripes; stripe += nwaves) {
+    uint64_t word = 0;
+    for (int step = 0; step < W; ++step) {
+      int64_t row = stripe * WAVE + step * L + sub;
+      bool rv = row < n && valid_bit(rvalid, row);
+      int32_t start = 0, len = 0;
+      if (rv) {
+        start = offsets[row];
+        len = offsets[row + 1] - start;
+      }
+      int hit = 0, unknown = 0;
+      for (int32_t i = sl; i < len; i += W) {
+        int64_t p = (int64_t)(start + i) - off0;
+        if (!valid_bit(pvalid, p)) unknown = 1;
+        else if ((pred[p] != 0) == (decide != 0)) hit = 1;
+      }
+      int st = hit | (unknown << 1);
+#pragma unroll
+      for (int j = W >> 1; j > 0; j >>= 1) st |= __shfl_xor(st, j, W);
+      bool any = (st & 1) != 0;
+      bool valid = rv && (any || !(st & 2));
+      uint64_t bal = __ballot(valid && sl == 0);  // bit sub * W = row's bit
+#pragma unroll
+      for (int g = 0; g < L; ++g)
+        word |= ((bal >> (g * W)) & 1ull) << (step * L + g);
+      if (sl == 0 && row < n)
+        out[row] = (valid && any == (decide != 0)) ? 1 : 0;
+    }
+    if (lane == 0) vout[stripe] = word;
+  }
+}
+
 // ---- host side -----------------------------------------------------------
 
 template <typename F>
@@ -628,6 +705,29 @@ void hipdf_list_union_map(const void* ascan, const void* aoffsets,
                      (const int32_t*)aoffsets, atotal, (const int64_t*)bscan,
                      (const int32_t*)boffsets, btotal, n, (int32_t)bbase,
                      (int32_t*)new_offs, (int32_t*)idx);
+}
+
+void hipdf_list_elem_rows(const void* offsets, int64_t n, void* rowid,
+                          void* pos, int64_t total, hipStream_t stream) {
+  if (n <= 0 || total <= 0) return;
+  hipLaunchKernelGGL(k_list_elem_rows, flat_grid(total), dim3(HIPDF_BLOCK), 0,
+                     stream, (const int32_t*)offsets, n, (int32_t*)rowid,
+                     (int32_t*)pos, total);
+}
+
+void hipdf_list_bool_reduce(const void* pred, const void* pvalid,
+                            const void* offsets, const void* rvalid, int w,
+                            int mode, void* out, void* vout, int64_t n,
+                            hipStream_t stream) {
+  if (n <= 0) return;
+  int64_t waves = (n + WAVE - 1) / WAVE;  // one wave per 64-row stripe
+  dispatch_width(w, [&]<int W>() {
+    hipLaunchKernelGGL((k_list_bool_reduce<W>), flat_grid(waves * WAVE),
+                       dim3(HIPDF_BLOCK), 0, stream, (const uint8_t*)pred,
+                       (const uint64_t*)pvalid, (const int32_t*)offsets,
+                       (const uint64_t*)rvalid, mode == 0 ? 1 : 0,
+                       (uint8_t*)out, (uint64_t*)vout, n);
+  });
 }
 
 }  // extern "C"

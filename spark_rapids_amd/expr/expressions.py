@@ -7,9 +7,13 @@ on the CPU backend or on the GPU backend depending on where the batch lives.
 """
 from __future__ import annotations
 
+import inspect
+import itertools
 from typing import Optional, Sequence
 
-from ..column import Column, ColumnBatch, Schema
+import numpy as np
+
+from ..column import Column, ColumnBatch, Field, Schema
 from ..types import (BOOL, DType, FLOAT64, INT32, INT64, STRING, TypeId,
                      _adjust_decimal, as_decimal, decimal_arith_type, promote)
 from .. import ops
@@ -207,6 +211,27 @@ class Expression:
         when they share none, both are non-empty and either holds a null,
         else false (Spark arrays_overlap)."""
         return ArraysOverlap(self, other)
+
+    def transform(self, f) -> "ArrayTransform":
+        """Apply `f` to every element of a LIST value (Spark transform).
+        `f` is a python callable of the element, or of the element and its
+        0-based position; it is called once to trace the lambda body."""
+        return ArrayTransform(self, _trace_lambda("transform", f, 2))
+
+    def filter(self, f) -> "ArrayFilter":
+        """Keep the elements of a LIST value for which `f(x)` or `f(x, i)`
+        is true (Spark filter)."""
+        return ArrayFilter(self, _trace_lambda("filter", f, 2))
+
+    def exists(self, f) -> "ArrayExists":
+        """True when `f(x)` is true for an element of a LIST value, NULL
+        when none is and one is NULL, else false (Spark exists)."""
+        return ArrayExists(self, _trace_lambda("exists", f, 1))
+
+    def forall(self, f) -> "ArrayForAll":
+        """False when `f(x)` is false for an element of a LIST value, NULL
+        when none is and one is NULL, else true (Spark forall)."""
+        return ArrayForAll(self, _trace_lambda("forall", f, 1))
 
     def regexp_extract(self, pattern: str, group: int = 1) -> "RegexpExtract":
         return RegexpExtract(self, pattern, group)
@@ -921,6 +946,279 @@ class ArraysOverlap(_ArraySetOp):
     def dtype(self, schema: Schema) -> DType:
         self._list_dtype(schema)
         return DType.bool_()
+
+
+_lambda_ids = itertools.count()
+
+
+class LambdaVariable(Expression):
+    """An argument of a lambda: the element `x` or its 0-based position `i`.
+    Deliberately not a ColumnRef, so column pruning never mistakes it for a
+    column of the input. `column` is the unique name it goes by in the
+    element schema, which keeps it apart from an outer column of the same
+    name and from the `x` of a sibling lambda."""
+
+    def __init__(self, name: str):
+        self.name = name
+        self.column = f"{name}#{next(_lambda_ids)}"
+
+    def dtype(self, schema: Schema) -> DType:
+        return schema.field(self.column).dtype
+
+    def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
+        return batch.columns[schema.index(self.column)]
+
+    def output_name(self) -> str:
+        return self.name
+
+    def __str__(self):
+        return self.name
+
+
+class LambdaFunction(Expression):
+    """`x -> body` or `(x, i) -> body`; typed and evaluated against the
+    element schema of the higher-order function that owns it."""
+
+    def __init__(self, args: Sequence[LambdaVariable], body: Expression):
+        self.args = tuple(args)
+        self.body = body
+
+    @property
+    def children(self):
+        return (self.body,)
+
+    def dtype(self, schema: Schema) -> DType:
+        return self.body.dtype(schema)
+
+    def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
+        return self.body.eval(batch, schema)
+
+    def __str__(self):
+        names = ", ".join(a.name for a in self.args)
+        return f"{names if len(self.args) == 1 else f'({names})'} -> " \
+               f"{self.body}"
+
+
+def _free_lambda_vars(e: Expression) -> list:
+    """LambdaVariables under `e` that no LambdaFunction under `e` binds."""
+    if isinstance(e, LambdaVariable):
+        return [e]
+    if isinstance(e, LambdaFunction):
+        return [v for v in _free_lambda_vars(e.body)
+                if not any(v is a for a in e.args)]
+    return [v for c in e.children for v in _free_lambda_vars(c)]
+
+
+def _outer_refs(e: Expression, out: set) -> set:
+    if isinstance(e, ColumnRef):
+        out.add(e.name)
+    for c in e.children:
+        _outer_refs(c, out)
+    return out
+
+
+class _ArrayLambda(Expression):
+    """A LIST value and a lambda over its elements (reference analogue:
+    GpuArrayTransform / GpuArrayFilter / GpuArrayExists). The body is an
+    ordinary projection over the flattened child: one row per element,
+    holding the element, its position when the lambda names it, and the
+    outer columns the body refers to, gathered by the element-to-row map."""
+
+    fn = ""
+    max_args = 1
+    predicate = True
+
+    def __init__(self, child: Expression, function: LambdaFunction):
+        if not isinstance(function, LambdaFunction):
+            raise TypeError(f"{self.fn} needs a lambda, got "
+                            f"{type(function).__name__}")
+        if not 1 <= len(function.args) <= self.max_args:
+            raise ValueError(
+                f"{self.fn} takes a lambda of "
+                f"{'one argument' if self.max_args == 1 else 'one or two arguments'}"
+                f", got {len(function.args)}")
+        free = [v for v in _free_lambda_vars(function.body)
+                if not any(v is a for a in function.args)]
+        if free:
+            raise NotImplementedError(
+                f"{self.fn}: a lambda nested in the body of another lambda "
+                f"cannot refer to the outer lambda's variable {free[0]}")
+        self.child = child
+        self.function = function
+
+    @property
+    def children(self):
+        return (self.child, self.function)
+
+    def _var_fields(self, schema: Schema) -> list:
+        cdt = self.child.dtype(schema)
+        if cdt.id is not TypeId.LIST:
+            raise TypeError(f"{self.fn} needs an array input, got {cdt}")
+        args = self.function.args
+        return [Field(args[0].column, cdt.children[0])] + \
+            [Field(a.column, INT32, False) for a in args[1:]]
+
+    def element_schema(self, schema: Schema) -> Schema:
+        """The schema the body is typed against: the outer schema plus the
+        lambda variables."""
+        return Schema(list(schema.fields) + self._var_fields(schema))
+
+    def _body_dtype(self, schema: Schema) -> DType:
+        bt = self.function.dtype(self.element_schema(schema))
+        if self.predicate and bt.id is not TypeId.BOOL:
+            raise TypeError(f"{self.fn} needs a boolean lambda body, got {bt}")
+        return bt
+
+    def _finish(self, arr: Column, res: Column, span) -> Column:
+        raise NotImplementedError
+
+    def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
+        bt = self._body_dtype(schema)
+        arr = self.child.eval(batch, schema)
+        span = off0, total = ops.list_span(arr)
+        if total == 0:
+            # nothing to evaluate the body on: an empty column of its type
+            return self._finish(
+                arr, Column.from_pylist([], bt).to(arr.device), span)
+        body = self.function.body
+        args = self.function.args
+        used = _free_lambda_vars(body)
+        elems = arr.child
+        if off0 != 0 or total != elems.size:
+            idx = Column.from_numpy(
+                np.arange(off0, off0 + total, dtype=np.int32),
+                device=arr.device)
+            elems = ops.gather(ColumnBatch([elems], elems.size), idx,
+                               negatives=False).columns[0]
+        names = _outer_refs(body, set())
+        outer = [f for f in schema.fields if f.name in names]
+        with_pos = len(args) > 1 and any(v is args[1] for v in used)
+        fields = self._var_fields(schema)[:2 if with_pos else 1]
+        cols = [elems]
+        if outer or with_pos:
+            rowid, pos = ops.list_element_rows(arr, with_pos, span)
+            if with_pos:
+                cols.append(pos)
+            if outer:
+                src = ColumnBatch([batch.columns[schema.index(f.name)]
+                                   for f in outer], batch.num_rows)
+                cols += ops.gather(src, rowid, negatives=False).columns
+                fields += outer
+        res = body.eval(ColumnBatch(cols, total), Schema(fields))
+        return self._finish(arr, res, span)
+
+    def __str__(self):
+        return f"{self.fn}({self.child}, {self.function})"
+
+
+class ArrayTransform(_ArrayLambda):
+    """transform(a, x -> f) / transform(a, (x, i) -> f): the body's value
+    for every element; offsets and row validity are the input's."""
+
+    fn = "transform"
+    max_args = 2
+    predicate = False
+
+    def dtype(self, schema: Schema) -> DType:
+        return DType.list_(self._body_dtype(schema))
+
+    def _finish(self, arr: Column, res: Column, span) -> Column:
+        n = arr.size
+        offs = arr.offsets[:n + 1]
+        if span[0]:
+            offs = ops.binary_op_scalar(
+                "sub", Column(INT32, n + 1, offs, None, null_count=0),
+                span[0], INT32).data
+        return Column(DType.list_(res.dtype), n, arr.data, arr.validity, offs,
+                      arr._null_count, res)
+
+
+class ArrayFilter(_ArrayLambda):
+    """filter(a, x -> p) / filter(a, (x, i) -> p): the elements whose
+    predicate is true, order kept; false and NULL drop the element."""
+
+    fn = "filter"
+    max_args = 2
+
+    def dtype(self, schema: Schema) -> DType:
+        self._body_dtype(schema)
+        return self.child.dtype(schema)
+
+    def _finish(self, arr: Column, res: Column, span) -> Column:
+        return ops.array_filter(arr, res, span)
+
+
+class ArrayExists(_ArrayLambda):
+    """exists(a, x -> p), three-valued: true if any predicate is true, else
+    NULL if any is NULL, else false."""
+
+    fn = "exists"
+
+    def dtype(self, schema: Schema) -> DType:
+        self._body_dtype(schema)
+        return BOOL
+
+    def _finish(self, arr: Column, res: Column, span) -> Column:
+        return ops.array_exists(arr, res, span)
+
+
+class ArrayForAll(_ArrayLambda):
+    """forall(a, x -> p): false if any predicate is false, else NULL if any
+    is NULL, else true."""
+
+    fn = "forall"
+
+    def dtype(self, schema: Schema) -> DType:
+        self._body_dtype(schema)
+        return BOOL
+
+    def _finish(self, arr: Column, res: Column, span) -> Column:
+        return ops.array_forall(arr, res, span)
+
+
+def _trace_lambda(fn: str, f, max_args: int) -> LambdaFunction:
+    """Call the python callable `f` once with LambdaVariables named after
+    its parameters and take what it returns as the lambda body."""
+    if isinstance(f, LambdaFunction):
+        return f
+    if not callable(f):
+        raise TypeError(f"{fn} needs a callable, got {type(f).__name__}")
+    try:
+        params = list(inspect.signature(f).parameters.values())
+    except (TypeError, ValueError) as ex:
+        raise TypeError(f"{fn}: cannot read the callable's signature: {ex}")
+    plain = (inspect.Parameter.POSITIONAL_ONLY,
+             inspect.Parameter.POSITIONAL_OR_KEYWORD)
+    if not 1 <= len(params) <= max_args or \
+            any(p.kind not in plain for p in params):
+        raise ValueError(
+            f"{fn} takes a callable of "
+            f"{'one argument' if max_args == 1 else 'one or two arguments'}"
+            f", got {inspect.signature(f)}")
+    args = [LambdaVariable(p.name) for p in params]
+    body = f(*args)
+    if not isinstance(body, (Expression, bool, int, float, str)):
+        raise TypeError(f"{fn}: the callable returned "
+                        f"{type(body).__name__}, not an expression")
+    return LambdaFunction(args, _as_expr(body))
+
+
+def transform(a, f) -> ArrayTransform:
+    """transform(a, lambda x: ...) or transform(a, lambda x, i: ...)."""
+    return _as_expr(a).transform(f)
+
+
+def filter_(a, f) -> ArrayFilter:
+    """filter(a, lambda x: ...) or filter(a, lambda x, i: ...)."""
+    return _as_expr(a).filter(f)
+
+
+def exists(a, f) -> ArrayExists:
+    return _as_expr(a).exists(f)
+
+
+def forall(a, f) -> ArrayForAll:
+    return _as_expr(a).forall(f)
 
 
 class HostStringFn(Expression):

@@ -108,6 +108,45 @@ def arrays_overlap(a: Column, b: Column) -> Column:
     return backend_for(a, b).arrays_overlap(a, b)
 
 
+def list_span(col: Column) -> Tuple[int, int]:
+    """(offsets[0], offsets[n] - offsets[0]) of a LIST column: where its
+    elements start in the child and how many there are. The one host read
+    of the higher-order functions; pass it on as `span` to spare the ops
+    below their own."""
+    return backend_for(col).list_span(col)
+
+
+def list_element_rows(col: Column, with_pos: bool = True,
+                      span: Optional[Tuple[int, int]] = None):
+    """(rowid, pos): two int32 columns with one row per element of the LIST
+    column from offsets[0] — the row that owns the element and its 0-based
+    position in that row (None when with_pos is false). rowid gathers outer
+    columns down to the elements for a lambda body."""
+    return backend_for(col).list_element_rows(col, with_pos, span)
+
+
+def array_filter(col: Column, pred: Column,
+                 span: Optional[Tuple[int, int]] = None) -> Column:
+    """filter(array, x -> pred): `pred` is a BOOL column with one row per
+    element from offsets[0]; elements whose predicate is false or NULL
+    drop, order kept, null rows stay null (GpuArrayFilter analogue)."""
+    return backend_for(col, pred).array_filter(col, pred, span)
+
+
+def array_exists(col: Column, pred: Column,
+                 span: Optional[Tuple[int, int]] = None) -> Column:
+    """exists(array, x -> pred), three-valued: true if any predicate is
+    true, else NULL if any is NULL, else false (GpuArrayExists analogue)."""
+    return backend_for(col, pred).array_exists(col, pred, span)
+
+
+def array_forall(col: Column, pred: Column,
+                 span: Optional[Tuple[int, int]] = None) -> Column:
+    """forall(array, x -> pred): false if any predicate is false, else NULL
+    if any is NULL, else true."""
+    return backend_for(col, pred).array_forall(col, pred, span)
+
+
 def map_keys(col: Column) -> Column:
     """MAP -> LIST<key>: shares the offsets and the entry key child
     buffer (zero-copy, reference GpuMapKeys)."""

@@ -820,6 +820,76 @@ def arrays_overlap(a: Column, b: Column) -> Column:
     return Column.from_pylist(out, DType.bool_())
 
 
+def list_span(col: Column):
+    """(first offset, child rows covered)."""
+    n = col.size
+    if n == 0:
+        return 0, 0
+    offs = col.offsets.numpy()
+    return int(offs[0]), int(offs[n]) - int(offs[0])
+
+
+def list_element_rows(col: Column, with_pos: bool = True, span=None):
+    """(rowid, pos): int32 columns with one row per element from
+    offsets[0], the owning row and the 0-based place in it (pos is None
+    unless asked for)."""
+    n = col.size
+    offs = col.offsets.numpy()[:n + 1].astype(np.int64)
+    lens = offs[1:] - offs[:-1]
+    rowid = np.repeat(np.arange(n, dtype=np.int32), lens)
+    pos = None
+    if with_pos:
+        starts = np.repeat(offs[:-1] - (offs[0] if n else 0), lens)
+        pos = _make((np.arange(len(rowid)) - starts).astype(np.int32), None,
+                    DType.int32())
+    return _make(rowid, None, DType.int32()), pos
+
+
+def _array_pred_rows(col: Column, pred: Column):
+    """Per row: None for a null row, else its list of (element, predicate)
+    pairs, the predicate being True, False or None."""
+    off0, total = list_span(col)
+    if pred.dtype.id is not TypeId.BOOL or pred.size != total:
+        raise ValueError(f"predicate of {pred.size} {pred.dtype} rows for "
+                         f"{total} array elements")
+    flags = pred.to_pylist()
+    offs = col.offsets.numpy()
+    out = []
+    for r, v in enumerate(col.to_pylist()):
+        out.append(None if v is None else
+                   list(zip(v, flags[offs[r] - off0:offs[r + 1] - off0])))
+    return out
+
+
+def array_filter(col: Column, pred: Column, span=None) -> Column:
+    """Keep the elements whose predicate is true; false and null drop."""
+    out = [None if v is None else [x for x, p in v if p is True]
+           for v in _array_pred_rows(col, pred)]
+    return Column.from_pylist(out, col.dtype)
+
+
+def array_exists(col: Column, pred: Column, span=None) -> Column:
+    """True if any predicate is true, else NULL if any is null, else
+    false; NULL for a null row."""
+    out = []
+    for v in _array_pred_rows(col, pred):
+        ps = None if v is None else [p for _, p in v]
+        out.append(None if ps is None else True if True in ps
+                   else None if None in ps else False)
+    return Column.from_pylist(out, DType.bool_())
+
+
+def array_forall(col: Column, pred: Column, span=None) -> Column:
+    """False if any predicate is false, else NULL if any is null, else
+    true; NULL for a null row."""
+    out = []
+    for v in _array_pred_rows(col, pred):
+        ps = None if v is None else [p for _, p in v]
+        out.append(None if ps is None else False if False in ps
+                   else None if None in ps else True)
+    return Column.from_pylist(out, DType.bool_())
+
+
 def map_get(col: Column, key) -> Column:
     out = []
     for v in col.to_pylist():  # dicts (last-win on duplicate keys)

@@ -1091,6 +1091,97 @@ def arrays_overlap(a: Column, b: Column) -> Column:
     return Column(DType.bool_(), n, out, ov, null_count=None)
 
 
+# higher-order functions: the lambda body runs as ordinary column kernels
+# over the flattened child; these map elements to rows and fold a predicate
+# column (one BOOL per element from offsets[0]) back into rows
+
+def list_span(col: Column):
+    """(first offset, child rows covered) — the one host read."""
+    n = col.size
+    if n == 0:
+        return 0, 0
+    off0, offn = (int(x) for x in col.offsets[0:n + 1:n].tolist())
+    return off0, offn - off0
+
+
+def list_element_rows(col: Column, with_pos: bool = True, span=None):
+    """(rowid, pos): int32 columns with one row per element from
+    offsets[0], the owning row and the 0-based place in it (pos is None
+    unless asked for)."""
+    off0, total = span or list_span(col)
+    rowid = torch.empty(max(total, 1), dtype=torch.int32,
+                        device="cuda")[:total]
+    pos = torch.empty_like(rowid) if with_pos else None
+    ext.list_elem_rows(col.offsets.data_ptr(), col.size, rowid.data_ptr(),
+                       _ptr(pos), total, _stream())
+    return (Column(DType.int32(), total, rowid, None, null_count=0),
+            None if pos is None else
+            Column(DType.int32(), total, pos, None, null_count=0))
+
+
+def _check_pred(pred: Column, total: int) -> None:
+    if pred.dtype.id is not TypeId.BOOL or pred.size != total:
+        raise ValueError(f"predicate of {pred.size} {pred.dtype} rows for "
+                         f"{total} array elements")
+
+
+def array_filter(col: Column, pred: Column, span=None) -> Column:
+    """Keep the elements whose predicate is true and not null, order kept;
+    the compaction is array_distinct's."""
+    n = col.size
+    if n == 0:
+        return Column.from_pylist([], col.dtype).cuda()
+    off0, total = span or list_span(col)
+    _check_pred(pred, total)
+    if total == 0:
+        return _list_with_child(col, _list_rebased_offsets(col, off0),
+                                _empty_col(col.child.dtype))
+    keep = pred.data[:total]
+    if pred.validity is not None:
+        ok = torch.empty(total, dtype=torch.uint8, device="cuda")
+        ext.mask_expand(pred.validity.data_ptr(), ok.data_ptr(), False,
+                        total, _stream())
+        keep = binary_op("and", _flag_col(keep), _flag_col(ok),
+                         DType.bool_()).data
+    new_offs, child = _list_compact(col, keep, off0, total)
+    return _list_with_child(col, new_offs, child)
+
+
+def _list_bool_reduce(col: Column, pred: Column, mode: int,
+                      span) -> Column:
+    n = col.size
+    if n == 0:
+        return _empty_col(DType.bool_())
+    _, total = span or list_span(col)
+    _check_pred(pred, total)
+    if total == 0:  # every row is empty or null
+        v = col.validity.clone() if col.validity is not None else None
+        return Column(DType.bool_(), n,
+                      torch.full((n,), mode, dtype=torch.uint8,
+                                 device="cuda"), v, null_count=col._null_count)
+    out = torch.empty(n, dtype=torch.uint8, device="cuda")
+    ov = _alloc_mask(n)
+    # lanes per row from the mean length: no maximum-length sync, and the
+    # stride covers the rows that are longer
+    ext.list_bool_reduce(pred.data.data_ptr(), _ptr(pred.validity),
+                         col.offsets.data_ptr(), _ptr(col.validity),
+                         _list_group_width(-(-total // n)), mode,
+                         out.data_ptr(), ov.data_ptr(), n, _stream())
+    return Column(DType.bool_(), n, out, ov, null_count=None)
+
+
+def array_exists(col: Column, pred: Column, span=None) -> Column:
+    """True when a predicate of the row is true, else NULL when one is
+    null, else false (list_bool_reduce)."""
+    return _list_bool_reduce(col, pred, 0, span)
+
+
+def array_forall(col: Column, pred: Column, span=None) -> Column:
+    """False when a predicate of the row is false, else NULL when one is
+    null, else true."""
+    return _list_bool_reduce(col, pred, 1, span)
+
+
 def _array_extreme(col: Column, is_max: bool) -> Column:
     n = col.size
     s = _stream()

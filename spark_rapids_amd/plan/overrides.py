@@ -13,7 +13,7 @@ from typing import List, Optional
 
 from ..config import RapidsConf
 from ..config import ALLOW_INCOMPAT as _ALLOW_INCOMPAT
-from ..expr.expressions import (_decimal_exact,
+from ..expr.expressions import (_decimal_exact, _outer_refs,
                                 Alias, BinaryExpr, CaseWhen, CastExpr,
                                 Coalesce, ColumnRef, Expression, IsNull,
                                 Literal, Round, StringPredicate, Substring,
@@ -71,6 +71,8 @@ _ARRAY_FN_NAMES = {"SortArray": "sort_array", "ArraySort": "array_sort",
                    "ArraysOverlap": "arrays_overlap"}
 _ARRAY_SET_OPS = ("ArrayUnion", "ArrayIntersect", "ArrayExcept",
                   "ArraysOverlap")
+_ARRAY_LAMBDAS = ("ArrayTransform", "ArrayFilter", "ArrayExists",
+                  "ArrayForAll")
 
 
 class TagReason:
@@ -185,6 +187,14 @@ class Tagger:
                     out.append(f"{fn} over decimal128 elements on CPU")
                 elif not (et.is_fixed_width or et.id is TypeId.STRING):
                     out.append(f"{fn} over {et} elements on CPU")
+        elif type(e).__name__ == "LambdaVariable":
+            pass
+        elif type(e).__name__ in _ARRAY_LAMBDAS:
+            # the argument lives in the outer schema, the body in the
+            # element schema (outer columns plus the lambda variables), so
+            # each is tagged here and the recursion below must not run
+            self._tag_array_lambda(e, schema, out)
+            return
         elif type(e).__name__ in ("ArraySize", "ElementAt"):
             cdt = e.child.dtype(schema)
             if cdt.id is TypeId.MAP and type(e).__name__ == "ElementAt" \
@@ -221,6 +231,35 @@ class Tagger:
             out.append(f"expression {type(e).__name__} not supported on GPU")
         for c in e.children:
             self._tag_expr(c, schema, out)
+
+    def _tag_array_lambda(self, e, schema, out: List[str]):
+        """transform / filter / exists / forall: the body runs as ordinary
+        column kernels over the flattened child, so whatever its own
+        tagging allows is allowed (decimal128 elements included — these
+        functions never compare elements themselves)."""
+        fn = e.fn
+        self._tag_expr(e.child, schema, out)
+        if not self.conf.expr_enabled(type(e).__name__):
+            out.append(f"expression {type(e).__name__} disabled by conf")
+        cdt = e.child.dtype(schema)
+        if cdt.id is not TypeId.LIST:
+            out.append(f"{fn} needs an array input, got {cdt}")
+            return
+        if cdt.children[0].is_nested:
+            out.append(f"{fn} over nested elements on CPU")
+            return
+        es = e.element_schema(schema)
+        bt = e.function.dtype(es)
+        if bt.is_nested:
+            out.append(f"{fn} with a nested result type {bt} on CPU")
+        body: List[str] = []
+        self._tag_expr(e.function.body, es, body)
+        for name in sorted(_outer_refs(e.function.body, set())):
+            if name in schema.names and \
+                    schema.field(name).dtype.id in (TypeId.LIST, TypeId.MAP):
+                body.append(f"outer column {name} of type "
+                            f"{schema.field(name).dtype} on CPU")
+        out += [f"{fn} lambda body: {r}" for r in body]
 
     # ---- plan nodes ----------------------------------------------------
     def exec_reasons(self, node: L.LogicalPlan) -> List[str]:

@@ -28,7 +28,7 @@ _TOKEN_RE = re.compile(r"""
       (?P<num>\d+\.\d*(?:[eE][+-]?\d+)?|\.\d+|\d+(?:[eE][+-]?\d+)?)
     | (?P<str>'(?:[^'\\]|''|\\.)*')
     | (?P<name>[A-Za-z_][A-Za-z_0-9]*)
-    | (?P<op><=|>=|<>|!=|=|<|>|\+|-|\*|/|%|\(|\)|,|\.)
+    | (?P<op><=|>=|<>|!=|=|<|>|\+|->|-|\*|/|%|\(|\)|,|\.)
     )""", re.VERBOSE)
 
 _TYPES = {
@@ -40,6 +40,12 @@ _TYPES = {
 
 _AGG_FUNCS = {"sum", "avg", "count", "min", "max", "stddev", "variance",
               "collect_list", "collect_set"}
+
+
+# higher-order array functions: name -> expression class (which checks the
+# lambda's arity)
+_LAMBDA_FUNCS = {"transform": "ArrayTransform", "filter": "ArrayFilter",
+                 "exists": "ArrayExists", "forall": "ArrayForAll"}
 
 
 class SqlError(ValueError):
@@ -111,6 +117,8 @@ class Parser:
         self.toks = tokenize(text)
         self.i = 0
         self.session = session
+        # names bound by the lambdas being parsed, innermost last
+        self.lambda_scopes: List[dict] = []
 
     # -- token helpers ---------------------------------------------------
     def peek(self, k=0):
@@ -576,6 +584,9 @@ class Parser:
             if self.peek(1) == ("op", "("):
                 return self.parse_func()
             self.next()
+            for scope in reversed(self.lambda_scopes):
+                if t[1] in scope:
+                    return scope[t[1]]
             return ColumnRef(self.parse_qualified_suffix(t[1]))
         raise SqlError(f"unexpected token {t}")
 
@@ -598,6 +609,63 @@ class Parser:
         self.expect_kw("END")
         return CaseWhen(branches, else_e)
 
+    def _lambda_names(self) -> Optional[List[str]]:
+        """The parameter names when a lambda starts here (`x ->` or
+        `(x, i) ->`), consumed up to and including the arrow; else None
+        with nothing consumed."""
+        if self.peek()[0] == "name" and self.peek(1) == ("op", "->"):
+            names = [self.next()[1]]
+            self.next()
+            return names
+        if self.peek() != ("op", "("):
+            return None
+        k, names = 1, []
+        while self.peek(k)[0] == "name":
+            names.append(self.peek(k)[1])
+            k += 1
+            if self.peek(k) != ("op", ","):
+                break
+            k += 1
+        if not names or self.peek(k) != ("op", ")") \
+                or self.peek(k + 1) != ("op", "->"):
+            return None
+        self.i += k + 2
+        return names
+
+    def parse_lambda_func(self, name: str):
+        """transform / filter / exists / forall (array, lambda); the opening
+        parenthesis is already consumed."""
+        from ..expr import expressions as _ex
+
+        args = []
+        if not self.op(")"):
+            while True:
+                names = self._lambda_names()
+                if names is None:
+                    args.append(self.parse_expr())
+                else:
+                    if len(set(names)) != len(names):
+                        raise ValueError(
+                            f"{name}: duplicate lambda argument in {names}")
+                    variables = [_ex.LambdaVariable(n) for n in names]
+                    self.lambda_scopes.append(dict(zip(names, variables)))
+                    try:
+                        body = self.parse_expr()
+                    finally:
+                        self.lambda_scopes.pop()
+                    args.append(_ex.LambdaFunction(variables, body))
+                if not self.op(","):
+                    break
+            self.expect_op(")")
+        if len(args) != 2:
+            raise ValueError(f"{name} takes two arguments, an array and a "
+                             f"lambda, got {len(args)}")
+        if isinstance(args[0], _ex.LambdaFunction) or \
+                not isinstance(args[1], _ex.LambdaFunction):
+            raise ValueError(f"{name}: the second argument must be a lambda "
+                             "(x -> expr)")
+        return getattr(_ex, _LAMBDA_FUNCS[name])(args[0], args[1])
+
     @staticmethod
     def _int_arg(e) -> int:
         from ..expr.expressions import Literal, UnaryExpr
@@ -615,6 +683,8 @@ class Parser:
         if name == "count" and self.op("*"):
             self.expect_op(")")
             return A.count_star()
+        if name in _LAMBDA_FUNCS:
+            return self.parse_lambda_func(name)
         distinct = False
         if name in _AGG_FUNCS and self.kw("DISTINCT"):
             distinct = True

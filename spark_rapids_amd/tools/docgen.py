@@ -201,6 +201,20 @@ _EXPR_ROWS = [
      "distinct(a) without b's elements"),
     ("ArraysOverlap", "arrays_overlap", "GPU",
      "true / NULL (a null and no shared element) / false"),
+    ("ArrayTransform", "transform(a, x -> f) / (x, i) -> f / "
+     "col.transform(lambda x: ...)", "GPU*",
+     "body evaluated as column kernels over the flattened child, outer "
+     "columns gathered by the element-to-row map (lists.hip); the body "
+     "must be GPU-supported; nested element or result types CPU"),
+    ("ArrayFilter", "filter(a, x -> p) / (x, i) -> p", "GPU*",
+     "keep flags from the predicate, array_distinct's compaction; the "
+     "body must be GPU-supported; nested element types CPU"),
+    ("ArrayExists", "exists(a, x -> p)", "GPU*",
+     "three-valued per-row reduction (lists.hip); the body must be "
+     "GPU-supported; nested element types CPU"),
+    ("ArrayForAll", "forall(a, x -> p)", "GPU*",
+     "three-valued per-row reduction; the body must be GPU-supported; "
+     "nested element types CPU"),
     ("CreateArray", "from_pylist lists", "CPU", "construction host-side"),
     # misc
     ("Rand", "SampleHash deterministic draw", "GPU", "sample() lowering"),
