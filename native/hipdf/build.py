@@ -31,6 +31,7 @@ KERNELS = [
     "kernels/sort.hip",
     "kernels/decode.hip",
     "kernels/csv.hip",
+    "kernels/json.hip",
     "kernels/strings.hip",
     "kernels/window.hip",
     "kernels/decimal128.hip",

@@ -460,6 +460,7 @@ PYBIND11_MODULE(hipdf, m) {
   BIND(json_field);
   BIND(byte_eq);
   BIND(csv_parse);
+  BIND(json_path);
 
   // ---- strings -----------------------------------------------------------
   BIND(str_cmp);

@@ -440,6 +440,21 @@ void hipdf_csv_parse(const void* bytes, const void* row_start,
                      void* out_sl, void* valid, void* unsupported,
                      int64_t nrows, hipStream_t stream);
 
+/* ---- get_json_object (kernels/json.hip) -------------------------------- */
+/* offsets int32[n+1] / bytes: the string column; valid: its mask or 0.
+ * steps: int32 triples [kind, a, b] per path step (kind 0 = key named
+ * names[a .. a+b), 1 = array index a). mode 0 (size pass) parses every row
+ * and writes out_len int64[n], src_start / src_len int32[n] (the matched
+ * value's span in bytes) and state uint8[n]: 0 NULL, 1 value, 2 left to the
+ * host. mode 1 (write pass) re-reads the span of each state == 1 row and
+ * writes its out_len normalised bytes at out_bytes + out_off[i] (int64) */
+void hipdf_json_path(const void* offsets, const void* bytes,
+                     const void* valid, const void* steps, const void* names,
+                     int nsteps, const void* out_off, void* out_len,
+                     void* src_start, void* src_len, void* state,
+                     void* out_bytes, int mode, int64_t n,
+                     hipStream_t stream);
+
 /* ---- strings (kernels/strings.hip) ------------------------------------- */
 /* op: 0 eq 1 ne 2 lt 3 le 4 gt 5 ge; out: uint8[n] */
 void hipdf_str_cmp(int op, const void* ao, const void* ab, const void* bo,

@@ -1366,13 +1366,21 @@ def concat_ws(sep: str, *exprs) -> ConcatWs:
 
 
 class GetJsonObject(Expression):
-    """get_json_object(col, '$.key'): top-level scalar extraction runs on
-    the GPU via the JSON field kernel (csv.hip k_json_field); nested paths
-    fall back to the CPU json parser (GpuGetJsonObject analogue)."""
+    """get_json_object(col, path): path is `$` followed by `.name`,
+    `['name']` and `[n]` steps (expr/json_path.py). On the GPU a validating
+    per-row JSON parser with a path matcher (json.hip) answers nested keys,
+    array indexes, escaped strings and object/array results itself, and
+    hands single rows whose host rendering it cannot reproduce (e.g. a float
+    spelt `1e2`) to the CPU json parser. Wildcards raise; a malformed path
+    gives NULL on every row (GpuGetJsonObject analogue)."""
 
     def __init__(self, child: Expression, path: str):
+        from . import json_path
+
         self.child = child
         self.path = path
+        # None for a malformed path; raises for a wildcard
+        self.steps = json_path.parse(path)
 
     @property
     def children(self):

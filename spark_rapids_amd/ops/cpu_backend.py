@@ -935,8 +935,11 @@ def concat_ws(sep: str, cols) -> Column:
 def get_json_object(col: Column, path: str) -> Column:
     import json as _json
 
-    assert path.startswith("$"), "json path must start with $"
-    keys = [k for k in path[1:].lstrip(".").split(".") if k]
+    from ..expr import json_path
+
+    steps = json_path.parse(path)
+    if steps is None:  # malformed path: NULL on every row
+        return Column.from_pylist([None] * col.size, DType.string())
     out = []
     for v in col.to_pylist():
         if v is None:
@@ -947,9 +950,13 @@ def get_json_object(col: Column, path: str) -> Column:
         except ValueError:
             out.append(None)
             continue
-        for k in keys:
-            if isinstance(cur, dict) and k in cur:
-                cur = cur[k]
+        for kind, arg in steps:
+            if kind == json_path.KEY and isinstance(cur, dict) \
+                    and arg in cur:
+                cur = cur[arg]
+            elif kind == json_path.INDEX and isinstance(cur, list) \
+                    and arg < len(cur):
+                cur = cur[arg]
             else:
                 cur = None
                 break

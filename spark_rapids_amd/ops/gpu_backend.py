@@ -424,42 +424,88 @@ def concat_ws(sep: str, cols) -> Column:
 
 
 def get_json_object(col: Column, path: str) -> Column:
-    """Top-level scalar key extraction ($.key) via k_json_field over the
-    string column's own row spans."""
-    keys = [k for k in path[1:].lstrip(".").split(".") if k]
-    if len(keys) != 1:
-        raise NotImplementedError("gpu get_json_object: nested path")
+    """Two passes of the row parser in json.hip. The size pass validates
+    every row, matches the path and gives each row's output length, the
+    matched value's span and a state (0 NULL, 1 value, 2 flagged); the write
+    pass re-reads only the spans. Flagged rows, whose host rendering the
+    device cannot reproduce, are compacted and answered by the CPU backend;
+    every other row stays on the device."""
+    from ..expr import json_path
+
     n = col.size
     s = _stream()
     if n == 0:
         return _empty_col(DType.string())
-    nameb = keys[0].encode("utf-8")
-    name_t = torch.frombuffer(bytearray(nameb), dtype=torch.uint8).cuda()
+    steps = json_path.parse(path)
+    if steps is None:  # malformed path: NULL on every row
+        return Column(DType.string(), n,
+                      torch.empty(0, dtype=torch.uint8, device="cuda"),
+                      torch.zeros(mask_nbytes(n), dtype=torch.uint8,
+                                  device="cuda"),
+                      torch.zeros(n + 1, dtype=torch.int32, device="cuda"),
+                      null_count=n)
+    flat, names = json_path.encode(steps)
+    steps_t = torch.tensor(flat or [0], dtype=torch.int32).cuda()
+    names_t = torch.frombuffer(bytearray(names or b"\x00"),
+                               dtype=torch.uint8).cuda()
+    lens = torch.empty(n, dtype=torch.int64, device="cuda")
     ss = torch.empty(n, dtype=torch.int32, device="cuda")
-    sl = torch.empty(n, dtype=torch.int64, device="cuda")
-    valid_u8 = torch.empty(n, dtype=torch.uint8, device="cuda")
-    unsupported = torch.zeros(1, dtype=torch.int32, device="cuda")
-    row_start = col.offsets[:n]
-    row_end = col.offsets[1:]
-    ext.json_field(col.data.data_ptr(), row_start.data_ptr(),
-                   row_end.data_ptr(), name_t.data_ptr(), len(nameb), 4,
-                   0, 0, ss.data_ptr(), sl.data_ptr(), valid_u8.data_ptr(),
-                   unsupported.data_ptr(), n, s)
-    if int(unsupported.item()) > 0:
+    sl = torch.empty(n, dtype=torch.int32, device="cuda")
+    state = torch.empty(n, dtype=torch.uint8, device="cuda")
+
+    def run(mode, out_off=0, out_bytes=0):
+        ext.json_path(col.offsets.data_ptr(), col.data.data_ptr(),
+                      _ptr(col.validity), steps_t.data_ptr(),
+                      names_t.data_ptr(), len(steps), out_off,
+                      lens.data_ptr(), ss.data_ptr(), sl.data_ptr(),
+                      state.data_ptr(), out_bytes, mode, n, s)
+
+    def scan():
+        scanned = torch.empty(n, dtype=torch.int64, device="cuda")
+        scratch = torch.empty(ext.scan_scratch_elems(n), dtype=torch.int64,
+                              device="cuda")
+        ext.exclusive_scan_i64(lens.data_ptr(), scanned.data_ptr(),
+                               scratch.data_ptr(), n, s)
+        return scanned, scratch[-1]
+
+    run(0)
+    flagged = state == 2
+    scanned, total_t = scan()
+    # the one host read: output bytes and how many rows the host must answer
+    total, nflag = torch.stack((total_t, flagged.sum())).tolist()
+    host = None
+    if nflag:
         from . import cpu_backend
 
-        return cpu_backend.get_json_object(col.cpu(), path).cuda()
-    out = _strings_from_spans(col, ss, sl, n, s)
-    from ..column import mask_nbytes
-
-    v64 = torch.empty(n, dtype=torch.int64, device="cuda")
-    ext.cast(0, 4, valid_u8.data_ptr(), v64.data_ptr(), n, s)
+        fidx = torch.nonzero(flagged).flatten().to(torch.int32)
+        host = cpu_backend.get_json_object(
+            _gather_col(col, fidx, nflag, maybe_negative=False).cpu(),
+            path).cuda()
+        ho = host.offsets.to(torch.int64)
+        hlens = ho[1:] - ho[:-1]
+        lens[fidx.long()] = hlens
+        scanned, total_t = scan()
+        total = int(total_t.item())
+    out_bytes = torch.empty(max(total, 1), dtype=torch.uint8,
+                            device="cuda")[:total]
+    if total:
+        run(1, scanned.data_ptr(), out_bytes.data_ptr())
+    if host is not None and host.data.numel():
+        hdst = scanned[fidx.long()]
+        ext.substr_copy(host.data.data_ptr(), host.offsets.data_ptr(),
+                        hlens.data_ptr(), hdst.data_ptr(),
+                        out_bytes.data_ptr(), nflag, s)
+    offs = torch.empty(n + 1, dtype=torch.int32, device="cuda")
+    ext.narrow_i64_i32(scanned.data_ptr(), offs.data_ptr(), n, s)
+    offs[n] = total
+    v64 = state.to(torch.int64)
+    if host is not None and host.validity is not None:
+        hv = torch.empty(nflag, dtype=torch.uint8, device="cuda")
+        ext.mask_expand(host.validity.data_ptr(), hv.data_ptr(), 0, nflag, s)
+        v64[fidx.long()] = hv.to(torch.int64)
     mask = torch.empty(mask_nbytes(n), dtype=torch.uint8, device="cuda")
     ext.mask_from_nonzero(v64.data_ptr(), mask.data_ptr(), n, s)
-    if col.validity is not None:
-        mask = _and_masks(col.validity, mask)
-    return Column(DType.string(), n, out.data, mask, out.offsets,
-                  null_count=None)
+    return Column(DType.string(), n, out_bytes, mask, offs, null_count=None)
 
 
 def regexp_extract_all(col: Column, pattern: str, group: int) -> Column:

@@ -155,9 +155,11 @@ class Tagger:
         elif type(e).__name__ == "ConcatWs":
             pass
         elif type(e).__name__ == "GetJsonObject":
-            keys = [k for k in e.path[1:].lstrip(".").split(".") if k]
-            if len(keys) != 1:
-                out.append("nested json paths run on CPU")
+            from ..expr.json_path import MAX_DEVICE_STEPS
+
+            if e.steps is not None and len(e.steps) > MAX_DEVICE_STEPS:
+                out.append(f"json paths of more than {MAX_DEVICE_STEPS} "
+                           "steps run on CPU")
         elif type(e).__name__ == "CpuBridge":
             return  # bridged subtree runs on host by design
         elif type(e).__name__ == "StrSplit":

@@ -117,7 +117,11 @@ _EXPR_ROWS = [
     ("Reverse", "k_str_reverse", "GPU", "codepoint order"),
     ("StringRepeat", "HostStringFn", "CPU", ""),
     ("StringTranslate", "HostStringFn", "CPU", ""),
-    ("GetJsonObject", "json key search kernel", "GPU*", "top-level keys; nested paths CPU"),
+    ("GetJsonObject", "validating JSON path kernel (json.hip)", "GPU*",
+     "nested keys, `[n]`, `['name']`, escapes; rows it cannot render "
+     "(e.g. `1e2`) and paths over 16 steps on CPU; no wildcards; an "
+     "object result keeps both members of a duplicated key, as Spark "
+     "does, where the CPU path keeps the last"),
     ("Murmur3Hash", "k_murmur3", "GPU", "spark-exact, seeds chain"),
     # datetime
     ("Year", "UnaryExpr year", "GPU", "civil calendar kernel"),
@@ -280,8 +284,8 @@ def supported_ops_doc() -> str:
                  "unary: `" + "`, `".join(sorted(ov._GPU_STRING_UNARY)) +
                  "`; plus `contains`, `starts_with`, `ends_with`, `like`, "
                  "`substring`, `split`, `concat_ws`, `element_at`/`size` "
-                 "over arrays, `get_json_object` (top-level keys) — "
-                 "strings.hip/csv.hip — and `rlike`, `regexp_extract`, "
+                 "over arrays — strings.hip — `get_json_object` (nested "
+                 "keys, array indexes, escaped strings; json.hip) and `rlike`, `regexp_extract`, "
                  "`regexp_extract_all`, `regexp_replace` (capture-group "
                  "regex VM, regex.hip, CPU fallback outside the subset)")
     lines += ["", "## Aggregate functions", "",
