@@ -461,6 +461,7 @@ PYBIND11_MODULE(hipdf, m) {
   BIND(byte_eq);
   BIND(csv_parse);
   BIND(json_path);
+  BIND(json_path_multi);
 
   // ---- strings -----------------------------------------------------------
   BIND(str_cmp);

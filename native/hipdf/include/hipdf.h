@@ -454,6 +454,19 @@ void hipdf_json_path(const void* offsets, const void* bytes,
                      void* src_start, void* src_len, void* state,
                      void* out_bytes, int mode, int64_t n,
                      hipStream_t stream);
+/* The size pass for npaths (1..8) paths over the same column in one parse
+ * per row. steps holds every path's triples one after another; path k owns
+ * step_cnt[k] of them from triple step_off[k] on (both int32[npaths], device
+ * memory), and every key name indexes the one names blob. The outputs hold
+ * npaths * n entries, path-major: entry k * n + i is what hipdf_json_path's
+ * size pass gives row i for path k alone. The write pass is hipdf_json_path
+ * mode 1 over those npaths * n entries. */
+void hipdf_json_path_multi(const void* offsets, const void* bytes,
+                           const void* valid, const void* steps,
+                           const void* step_off, const void* step_cnt,
+                           const void* names, int npaths, void* out_len,
+                           void* src_start, void* src_len, void* state,
+                           int64_t n, hipStream_t stream);
 
 /* ---- strings (kernels/strings.hip) ------------------------------------- */
 /* op: 0 eq 1 ne 2 lt 3 le 4 gt 5 ge; out: uint8[n] */

@@ -19,7 +19,7 @@ from .expr.expressions import (CaseWhen, ascii_, coalesce, col, concat_ws,
                                repeat_str, substring_index, translate,
                                date_add, date_sub,
                                datediff, dayofweek, greatest, hour, isin,
-                               least, lit, quarter, to_date,
+                               json_tuple, least, lit, quarter, to_date,
                                unix_timestamp,
                                minute, round_, second, when,
                                create_map, map_keys, map_values,

@@ -47,7 +47,11 @@ class DataFrame:
     where = filter
 
     def select(self, *exprs: Union[str, Expression]) -> "DataFrame":
-        es = [(_col(e) if isinstance(e, str) else e) for e in exprs]
+        # a list or tuple argument (what json_tuple returns) is spread
+        flat = []
+        for e in exprs:
+            flat.extend(e) if isinstance(e, (list, tuple)) else flat.append(e)
+        es = [(_col(e) if isinstance(e, str) else e) for e in flat]
         return DataFrame(self.session, L.Project(es, self.plan))
 
     def with_column(self, name: str, expr) -> "DataFrame":

@@ -455,10 +455,13 @@ class ColumnBatch:
     """A batch of columns — the unit flowing between physical operators
     (reference analogue: ColumnarBatch of GpuColumnVector)."""
 
-    __slots__ = ("columns", "num_rows")
+    __slots__ = ("columns", "num_rows", "memo")
 
     def __init__(self, columns: List[Column], num_rows: Optional[int] = None):
         self.columns = list(columns)
+        # columns an operator computed ahead for expression nodes it is about
+        # to evaluate over this batch, keyed by id(node); None: nothing
+        self.memo = None
         if num_rows is None:
             num_rows = columns[0].size if columns else 0
         self.num_rows = num_rows

@@ -212,6 +212,11 @@ CPU_BRIDGE = bool_conf(
     "Evaluate CPU-only expressions inside GPU projections via a host "
     "round-trip instead of demoting the whole project "
     "(GpuCpuBridgeExpression analogue).")
+JSON_COMBINE_PATHS = bool_conf(
+    "spark.rapids.sql.json.combinePaths.enabled", True,
+    "In a GPU project, answer all get_json_object / json_tuple paths over "
+    "the same column with one parse of each row instead of one parse per "
+    "path (GetJsonObjectCombiner analogue).")
 FILECACHE = bool_conf(
     "spark.rapids.filecache.enabled", False,
     "Cache decoded scan batches per (file, mtime) in host memory so "

@@ -249,6 +249,10 @@ class Expression:
     def get_json_object(self, path: str) -> "GetJsonObject":
         return GetJsonObject(self, path)
 
+    def json_tuple(self, *fields) -> list:
+        """One expression per top-level field, aliased c0, c1, ..."""
+        return json_tuple(self, *fields)
+
     def regexp_extract_all(self, pattern: str,
                            group: int = 1) -> "RegexpExtractAll":
         return RegexpExtractAll(self, pattern, group)
@@ -1372,7 +1376,11 @@ class GetJsonObject(Expression):
     array indexes, escaped strings and object/array results itself, and
     hands single rows whose host rendering it cannot reproduce (e.g. a float
     spelt `1e2`) to the CPU json parser. Wildcards raise; a malformed path
-    gives NULL on every row (GpuGetJsonObject analogue)."""
+    gives NULL on every row (GpuGetJsonObject analogue).
+
+    A GPU project that holds several of these over one child parses each row
+    once for all of them (ProjectExec) and leaves the columns in the batch's
+    memo, from which eval() takes its own."""
 
     def __init__(self, child: Expression, path: str):
         from . import json_path
@@ -1381,6 +1389,19 @@ class GetJsonObject(Expression):
         self.path = path
         # None for a malformed path; raises for a wildcard
         self.steps = json_path.parse(path)
+        self.text = None
+
+    @classmethod
+    def from_steps(cls, child: Expression, steps, text: str):
+        """The same expression for a path given as parsed steps (None: a
+        malformed path), which may hold key names that no path string can
+        spell. `text` is how the node prints."""
+        node = cls.__new__(cls)
+        node.child = child
+        node.path = None
+        node.steps = None if steps is None else list(steps)
+        node.text = text
+        return node
 
     @property
     def children(self):
@@ -1390,11 +1411,41 @@ class GetJsonObject(Expression):
         return STRING
 
     def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
-        return ops.get_json_object(self.child.eval(batch, schema),
-                                   self.path)
+        if batch.memo is not None:
+            fused = batch.memo.get(id(self))
+            if fused is not None:
+                return fused
+        child = self.child.eval(batch, schema)
+        if self.path is None:
+            return ops.get_json_object_multi(child, [self.steps])[0]
+        return ops.get_json_object(child, self.path)
 
     def __str__(self):
+        if self.path is None:
+            return self.text
         return f"get_json_object({self.child}, {self.path!r})"
+
+
+def json_tuple(e, *fields) -> list:
+    """json_tuple(e, f0, f1, ...): the top-level fields f0, f1, ... of the
+    JSON object in `e`, as expressions aliased c0, c1, ... Field i is
+    get_json_object with the single key step fields[i]: the name is a literal
+    key, never a path, so `a.b`, `x[0]`, `it's` and the empty string name
+    members. A None field gives NULL on every row (GpuJsonTuple analogue)."""
+    from . import json_path
+
+    if not fields:
+        raise ValueError("json_tuple needs at least one field")
+    child = _as_expr(e)
+    out = []
+    for i, f in enumerate(fields):
+        if f is not None and not isinstance(f, str):
+            raise TypeError("json_tuple fields are strings or None")
+        steps = None if f is None else [(json_path.KEY, f)]
+        node = GetJsonObject.from_steps(
+            child, steps, f"json_tuple({child}, {f!r})")
+        out.append(Alias(node, f"c{i}"))
+    return out
 
 
 class CpuBridge(Expression):

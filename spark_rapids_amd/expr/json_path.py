@@ -23,6 +23,9 @@ Step = Tuple[int, Union[str, int]]
 
 # paths longer than this run on the CPU (the tagger's bound)
 MAX_DEVICE_STEPS = 16
+# paths over one column that one device parse answers (kMaxFusedPaths in
+# native/hipdf/kernels/json_path.h); larger groups run in chunks
+MAX_FUSED_PATHS = 8
 
 
 def parse(path: str) -> Optional[List[Step]]:

@@ -192,6 +192,12 @@ def get_json_object(col: Column, path: str) -> Column:
     return backend_for(col).get_json_object(col, path)
 
 
+def get_json_object_multi(col: Column, steps_list) -> List[Column]:
+    """Several paths over one column, each given as parsed steps
+    (expr/json_path.py; None for a malformed path): one column per entry."""
+    return backend_for(col).get_json_object_multi(col, list(steps_list))
+
+
 def regexp_extract_all(col: Column, pattern: str, group: int) -> Column:
     return backend_for(col).regexp_extract_all(col, pattern, group)
 

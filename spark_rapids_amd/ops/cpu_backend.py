@@ -932,45 +932,63 @@ def concat_ws(sep: str, cols) -> Column:
     return Column.from_pylist(out, DType.string())
 
 
-def get_json_object(col: Column, path: str) -> Column:
+def _json_walk_render(doc, steps):
+    """The value `steps` selects in the parsed document, rendered as
+    get_json_object renders it; None where nothing is selected."""
     import json as _json
 
     from ..expr import json_path
 
-    steps = json_path.parse(path)
-    if steps is None:  # malformed path: NULL on every row
-        return Column.from_pylist([None] * col.size, DType.string())
-    out = []
-    for v in col.to_pylist():
-        if v is None:
-            out.append(None)
-            continue
-        try:
-            cur = _json.loads(v)
-        except ValueError:
-            out.append(None)
-            continue
-        for kind, arg in steps:
-            if kind == json_path.KEY and isinstance(cur, dict) \
-                    and arg in cur:
-                cur = cur[arg]
-            elif kind == json_path.INDEX and isinstance(cur, list) \
-                    and arg < len(cur):
-                cur = cur[arg]
-            else:
-                cur = None
-                break
-        if cur is None:
-            out.append(None)
-        elif isinstance(cur, str):
-            out.append(cur)
-        elif isinstance(cur, bool):
-            out.append("true" if cur else "false")
-        elif isinstance(cur, (dict, list)):
-            out.append(_json.dumps(cur, separators=(",", ":")))
+    cur = doc
+    for kind, arg in steps:
+        if kind == json_path.KEY and isinstance(cur, dict) \
+                and arg in cur:
+            cur = cur[arg]
+        elif kind == json_path.INDEX and isinstance(cur, list) \
+                and arg < len(cur):
+            cur = cur[arg]
         else:
-            out.append(_json.dumps(cur))
-    return Column.from_pylist(out, DType.string())
+            return None
+    if cur is None:
+        return None
+    if isinstance(cur, str):
+        return cur
+    if isinstance(cur, bool):
+        return "true" if cur else "false"
+    if isinstance(cur, (dict, list)):
+        return _json.dumps(cur, separators=(",", ":"))
+    return _json.dumps(cur)
+
+
+def get_json_object_multi(col: Column, steps_list) -> List[Column]:
+    """One column per entry of steps_list (parsed paths, expr/json_path.py;
+    None for a malformed path, which gives NULL on every row). Each row is
+    parsed once and walked once per path."""
+    import json as _json
+
+    outs = [[] for _ in steps_list]
+    for v in col.to_pylist():
+        doc, ok = None, False
+        if v is not None:
+            try:
+                doc, ok = _json.loads(v), True
+            except ValueError:
+                pass
+        for out, steps in zip(outs, steps_list):
+            out.append(_json_walk_render(doc, steps)
+                       if ok and steps is not None else None)
+    return [Column.from_pylist(out, DType.string()) for out in outs]
+
+
+def get_json_object_steps(col: Column, steps) -> Column:
+    """get_json_object for a path given as parsed steps."""
+    return get_json_object_multi(col, [steps])[0]
+
+
+def get_json_object(col: Column, path: str) -> Column:
+    from ..expr import json_path
+
+    return get_json_object_steps(col, json_path.parse(path))
 
 
 def regexp_extract_all(col: Column, pattern: str, group: int) -> Column:

@@ -431,19 +431,33 @@ def get_json_object(col: Column, path: str) -> Column:
     device cannot reproduce, are compacted and answered by the CPU backend;
     every other row stays on the device."""
     from ..expr import json_path
+    from . import cpu_backend
+
+    return _json_path_single(
+        col, json_path.parse(path),
+        lambda flagged_rows: cpu_backend.get_json_object(flagged_rows, path))
+
+
+def _all_null_strings(n: int) -> Column:
+    return Column(DType.string(), n,
+                  torch.empty(0, dtype=torch.uint8, device="cuda"),
+                  torch.zeros(mask_nbytes(n), dtype=torch.uint8,
+                              device="cuda"),
+                  torch.zeros(n + 1, dtype=torch.int32, device="cuda"),
+                  null_count=n)
+
+
+def _json_path_single(col: Column, steps, ask_host) -> Column:
+    """One path given as parsed steps; ask_host answers a host column of the
+    flagged rows."""
+    from ..expr import json_path
 
     n = col.size
     s = _stream()
     if n == 0:
         return _empty_col(DType.string())
-    steps = json_path.parse(path)
     if steps is None:  # malformed path: NULL on every row
-        return Column(DType.string(), n,
-                      torch.empty(0, dtype=torch.uint8, device="cuda"),
-                      torch.zeros(mask_nbytes(n), dtype=torch.uint8,
-                                  device="cuda"),
-                      torch.zeros(n + 1, dtype=torch.int32, device="cuda"),
-                      null_count=n)
+        return _all_null_strings(n)
     flat, names = json_path.encode(steps)
     steps_t = torch.tensor(flat or [0], dtype=torch.int32).cuda()
     names_t = torch.frombuffer(bytearray(names or b"\x00"),
@@ -475,12 +489,9 @@ def get_json_object(col: Column, path: str) -> Column:
     total, nflag = torch.stack((total_t, flagged.sum())).tolist()
     host = None
     if nflag:
-        from . import cpu_backend
-
         fidx = torch.nonzero(flagged).flatten().to(torch.int32)
-        host = cpu_backend.get_json_object(
-            _gather_col(col, fidx, nflag, maybe_negative=False).cpu(),
-            path).cuda()
+        host = ask_host(
+            _gather_col(col, fidx, nflag, maybe_negative=False).cpu()).cuda()
         ho = host.offsets.to(torch.int64)
         hlens = ho[1:] - ho[:-1]
         lens[fidx.long()] = hlens
@@ -506,6 +517,150 @@ def get_json_object(col: Column, path: str) -> Column:
     mask = torch.empty(mask_nbytes(n), dtype=torch.uint8, device="cuda")
     ext.mask_from_nonzero(v64.data_ptr(), mask.data_ptr(), n, s)
     return Column(DType.string(), n, out_bytes, mask, offs, null_count=None)
+
+
+def get_json_object_multi(col: Column, steps_list) -> List[Column]:
+    """get_json_object for several paths over one column: one column per
+    entry of steps_list (parsed steps; None, a malformed path, gives NULL on
+    every row). Equal entries are computed once, and up to MAX_FUSED_PATHS
+    distinct paths share one parse of each row."""
+    from ..expr import json_path
+    from . import cpu_backend
+
+    n = col.size
+    keys = [None if st is None else tuple(st) for st in steps_list]
+    distinct = list(dict.fromkeys(k for k in keys if k is not None))
+    done = {}
+    if n == 0:
+        return [_empty_col(DType.string()) for _ in keys]
+    m = json_path.MAX_FUSED_PATHS
+    for at in range(0, len(distinct), m):
+        chunk = distinct[at:at + m]
+        if len(chunk) == 1:
+            steps = list(chunk[0])
+            done[chunk[0]] = _json_path_single(
+                col, steps, lambda rows, steps=steps:
+                cpu_backend.get_json_object_steps(rows, steps))
+        else:
+            done.update(zip(chunk, _json_path_chunk(col, chunk)))
+    return [_all_null_strings(n) if k is None else done[k] for k in keys]
+
+
+def _json_path_chunk(col: Column, chunk) -> List[Column]:
+    """2..MAX_FUSED_PATHS distinct paths in one size launch, one scan and one
+    write launch. Every per-row array holds K * n entries, path-major, so
+    path k owns [k * n, (k + 1) * n) and its column is a slice."""
+    from ..expr import json_path
+    from . import cpu_backend
+
+    n = col.size
+    s = _stream()
+    K = len(chunk)
+    # the native call launches nothing for a group size it has no kernel for
+    assert 2 <= K <= json_path.MAX_FUSED_PATHS, K
+    kn = K * n
+    flat: List[int] = []
+    names = bytearray()
+    meta: List[int] = []       # step_off[K] then step_cnt[K]
+    for steps in chunk:
+        f, nm = json_path.encode(list(steps))
+        for t in range(0, len(f), 3):
+            if f[t] == json_path.KEY:
+                f[t + 1] += len(names)
+        meta.append(len(flat) // 3)
+        flat.extend(f)
+        names.extend(nm)
+    meta.extend(len(steps) for steps in chunk)
+    steps_t = torch.tensor(flat or [0], dtype=torch.int32).cuda()
+    meta_t = torch.tensor(meta, dtype=torch.int32).cuda()
+    names_t = torch.frombuffer(bytearray(names or b"\x00"),
+                               dtype=torch.uint8).cuda()
+    lens = torch.empty(kn, dtype=torch.int64, device="cuda")
+    ss = torch.empty(kn, dtype=torch.int32, device="cuda")
+    sl = torch.empty(kn, dtype=torch.int32, device="cuda")
+    state = torch.empty(kn, dtype=torch.uint8, device="cuda")
+    ext.json_path_multi(col.offsets.data_ptr(), col.data.data_ptr(),
+                        _ptr(col.validity), steps_t.data_ptr(),
+                        meta_t.data_ptr(), meta_t[K:].data_ptr(),
+                        names_t.data_ptr(), K, lens.data_ptr(),
+                        ss.data_ptr(), sl.data_ptr(), state.data_ptr(), n, s)
+
+    def scan():
+        scanned = torch.empty(kn, dtype=torch.int64, device="cuda")
+        scratch = torch.empty(ext.scan_scratch_elems(kn), dtype=torch.int64,
+                              device="cuda")
+        ext.exclusive_scan_i64(lens.data_ptr(), scanned.data_ptr(),
+                               scratch.data_ptr(), kn, s)
+        # the total, then each path's first output position
+        return scanned, torch.cat((scratch[-1:], scanned[::n]))
+
+    flagged = state == 2
+    scanned, ends_t = scan()
+    # the one host read: output bytes, where each path's bytes begin, and how
+    # many rows of each path the host must answer
+    stats = torch.cat((ends_t, flagged.view(K, n).sum(dim=1))).tolist()
+    total, base, nflags = stats[0], stats[1:K + 1], stats[K + 1:]
+    hosts = {}
+    for k, nflag in enumerate(nflags):
+        if not nflag:
+            continue
+        fidx = torch.nonzero(flagged[k * n:(k + 1) * n]).flatten()
+        host = cpu_backend.get_json_object_steps(
+            _gather_col(col, fidx.to(torch.int32), nflag,
+                        maybe_negative=False).cpu(), list(chunk[k])).cuda()
+        ho = host.offsets.to(torch.int64)
+        hlens = ho[1:] - ho[:-1]
+        at = fidx + k * n
+        lens[at] = hlens
+        hosts[k] = (host, hlens, at)
+    if hosts:
+        scanned, ends_t = scan()
+        ends = ends_t.tolist()
+        total, base = ends[0], ends[1:]
+    base.append(total)
+
+    # One buffer for all paths, so that one write launch fills it, but each
+    # column is a string column like any other: its data is the part of the
+    # buffer that holds its own bytes (16-byte aligned starts, as a fresh
+    # allocation's would be), its offsets start at 0 and end at data.numel().
+    # Consumers such as concat_batches rely on both. Offsets are per path,
+    # so int32 bounds a single path's bytes, never their sum.
+    sizes = [base[k + 1] - base[k] for k in range(K)]
+    starts, room = [], 0
+    for size in sizes:
+        starts.append(room)
+        room += (size + 15) // 16 * 16
+    place = torch.tensor([starts, base[:K], sizes], dtype=torch.int64).cuda()
+    rel = scanned.view(K, n) - place[1].view(K, 1)   # within the path's bytes
+    dst = (rel + place[0].view(K, 1)).view(-1)       # within the buffer
+    out_bytes = torch.empty(max(room, 1), dtype=torch.uint8, device="cuda")
+    if total:
+        ext.json_path(0, col.data.data_ptr(), 0, 0, 0, 0, dst.data_ptr(),
+                      lens.data_ptr(), ss.data_ptr(), sl.data_ptr(),
+                      state.data_ptr(), out_bytes.data_ptr(), 1, kn, s)
+    offs = torch.empty((K, n + 1), dtype=torch.int32, device="cuda")
+    offs[:, :n] = rel
+    offs[:, n] = place[2]
+    v64 = state.to(torch.int64)
+    for host, hlens, at in hosts.values():
+        if host.data.numel():
+            hdst = dst[at]
+            ext.substr_copy(host.data.data_ptr(), host.offsets.data_ptr(),
+                            hlens.data_ptr(), hdst.data_ptr(),
+                            out_bytes.data_ptr(), hlens.numel(), s)
+        if host.validity is not None:
+            hv = torch.empty(at.numel(), dtype=torch.uint8, device="cuda")
+            ext.mask_expand(host.validity.data_ptr(), hv.data_ptr(), 0,
+                            at.numel(), s)
+            v64[at] = hv.to(torch.int64)
+    out = []
+    for k in range(K):
+        mask = torch.empty(mask_nbytes(n), dtype=torch.uint8, device="cuda")
+        ext.mask_from_nonzero(v64[k * n:].data_ptr(), mask.data_ptr(), n, s)
+        out.append(Column(DType.string(), n,
+                          out_bytes[starts[k]:starts[k] + sizes[k]], mask,
+                          offs[k], null_count=None))
+    return out
 
 
 def regexp_extract_all(col: Column, pattern: str, group: int) -> Column:

@@ -494,8 +494,9 @@ def _convert(node: L.LogicalPlan, conf: RapidsConf, tagger: Tagger,
     if isinstance(node, L.Filter):
         return P.FilterExec(device, node.condition, kids[0])
     if isinstance(node, L.Project):
-        from ..config import CPU_BRIDGE
+        from ..config import CPU_BRIDGE, JSON_COMBINE_PATHS
 
+        combine = conf.get(JSON_COMBINE_PATHS)
         if not on_gpu and gpu_wanted and conf.get(CPU_BRIDGE) \
                 and conf.exec_enabled("Project"):
             from ..expr.expressions import CpuBridge
@@ -513,8 +514,10 @@ def _convert(node: L.LogicalPlan, conf: RapidsConf, tagger: Tagger,
                 inner = _ensure_device(
                     _convert(node.children[0], conf, tagger, gpu_wanted),
                     "cuda")
-                return P.ProjectExec("cuda", wrapped, inner, node.schema())
-        return P.ProjectExec(device, node.exprs, kids[0], node.schema())
+                return P.ProjectExec("cuda", wrapped, inner, node.schema(),
+                                     combine_json_paths=combine)
+        return P.ProjectExec(device, node.exprs, kids[0], node.schema(),
+                             combine_json_paths=combine)
     if isinstance(node, L.Expand):
         return P.ExpandExec(device, node.projections, kids[0], node.schema())
     if isinstance(node, L.Generate):

@@ -175,15 +175,67 @@ class FilterExec(PhysicalExec):
         return f"{self.name()}({self.condition})"
 
 
+def _json_path_groups(exprs: Sequence[Expression]) -> List[list]:
+    """The GetJsonObject nodes anywhere under `exprs`, grouped by child
+    expression, for the groups that hold two or more distinct paths: each
+    such group is answered by one parse of its child's rows
+    (GetJsonObjectCombiner analogue). Children are the same when they are
+    one object or refer to the same column. Inner nodes come before the nodes
+    built on them. Left alone: nodes evaluated elsewhere than over the
+    project's own batch (inside a lambda, behind the CPU bridge) and paths
+    beyond the device's bound."""
+    from ..expr.expressions import _free_lambda_vars
+    from ..expr.json_path import MAX_DEVICE_STEPS
+
+    groups: dict = {}
+    seen = set()
+
+    def visit(e):
+        kind = type(e).__name__
+        if kind in ("CpuBridge", "LambdaFunction"):
+            return
+        for c in e.children:
+            visit(c)
+        if kind != "GetJsonObject" or id(e) in seen:
+            return
+        seen.add(id(e))
+        if e.steps is not None and len(e.steps) > MAX_DEVICE_STEPS:
+            return
+        if _free_lambda_vars(e.child):
+            return
+        key = ("col", e.child.name) if isinstance(e.child, ColumnRef) \
+            else ("node", id(e.child))
+        groups.setdefault(key, []).append(e)
+
+    for e in exprs:
+        visit(e)
+    return [nodes for nodes in groups.values()
+            if len({tuple(n.steps) for n in nodes
+                    if n.steps is not None}) >= 2]
+
+
 class ProjectExec(PhysicalExec):
     def __init__(self, device: str, exprs: List[Expression], child: PhysicalExec,
-                 schema: Schema):
+                 schema: Schema, combine_json_paths: bool = False):
         super().__init__(device, schema, [child])
         self.exprs = exprs
+        self.json_groups = _json_path_groups(exprs) \
+            if combine_json_paths and self.gpu else []
 
     def execute(self) -> Iterator[ColumnBatch]:
         in_schema = self.children[0].schema
         for batch in self.children[0].execute():
+            if self.json_groups:
+                # the memo lives on a batch object of this call's own: the
+                # incoming one may be shared with other threads
+                batch = ColumnBatch(batch.columns, batch.num_rows)
+                batch.memo = {}
+                for nodes in self.json_groups:
+                    src = nodes[0].child.eval(batch, in_schema)
+                    fused = ops.get_json_object_multi(
+                        src, [n.steps for n in nodes])
+                    batch.memo.update(
+                        (id(n), c) for n, c in zip(nodes, fused))
             cols = [e.eval(batch, in_schema) for e in self.exprs]
             yield ColumnBatch(cols, batch.num_rows)
 

@@ -162,6 +162,13 @@ class Parser:
             star = True
         else:
             while True:
+                if self.peek()[0] == "name" and \
+                        self.peek()[1].lower() == "json_tuple" and \
+                        self.peek(1) == ("op", "("):
+                    items.extend(self.parse_json_tuple())
+                    if not self.op(","):
+                        break
+                    continue
                 e = self.parse_select_item()
                 alias = None
                 if self.kw("AS"):
@@ -324,6 +331,57 @@ class Parser:
         if limit is not None:
             df = df.limit(limit)
         return df
+
+    def parse_json_tuple(self):
+        """json_tuple(expr, 'f0', 'f1', ...) [AS (n0, n1, ...)] in a select
+        list: one (expr, alias) item per field, named c0, c1, ... unless the
+        AS list names them. A field is a string literal or NULL."""
+        from ..expr.expressions import json_tuple
+
+        self.next()
+        self.expect_op("(")
+        child = self.parse_expr()
+        fields = []
+        while self.op(","):
+            t = self.next()
+            if t[0] == "str":
+                fields.append(t[1])
+            elif t[0] == "name" and t[1].upper() == "NULL":
+                fields.append(None)
+            else:
+                raise SqlError("json_tuple fields must be string literals "
+                               f"or NULL, got {t[1]!r}")
+            if self.peek() not in (("op", ","), ("op", ")")):
+                raise SqlError("json_tuple fields must be string literals "
+                               f"or NULL, got an expression at {self.peek()}")
+        self.expect_op(")")
+        if not fields:
+            raise SqlError("json_tuple needs at least one field")
+        outs = json_tuple(child, *fields)
+        names = [None] * len(outs)  # the default c0, c1, ...
+        if not self.kw("AS"):
+            pass
+        elif not self.op("("):
+            # a single name without parentheses names a one-field tuple
+            t = self.next()
+            if t[0] != "name" or len(outs) != 1:
+                raise SqlError(f"json_tuple gives {len(outs)} columns: name "
+                               "them with AS (n0, n1, ...)")
+            names = [t[1]]
+        else:
+            names = []
+            while True:
+                t = self.next()
+                if t[0] != "name":
+                    raise SqlError(f"expected a column name at {t}")
+                names.append(t[1])
+                if not self.op(","):
+                    break
+            self.expect_op(")")
+            if len(names) != len(outs):
+                raise SqlError(f"json_tuple gives {len(outs)} columns, "
+                               f"AS names {len(names)}")
+        return [(o.child, nm or o.name) for o, nm in zip(outs, names)]
 
     def parse_table(self):
         name = self.next()[1]

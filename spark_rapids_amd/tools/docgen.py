@@ -121,7 +121,13 @@ _EXPR_ROWS = [
      "nested keys, `[n]`, `['name']`, escapes; rows it cannot render "
      "(e.g. `1e2`) and paths over 16 steps on CPU; no wildcards; an "
      "object result keeps both members of a duplicated key, as Spark "
-     "does, where the CPU path keeps the last"),
+     "does, where the CPU path keeps the last; in a GPU project, paths "
+     "over one column share one parse (up to 8 per kernel launch; "
+     "`spark.rapids.sql.json.combinePaths.enabled`)"),
+    ("JsonTuple", "multi-path JSON kernel (json.hip), one parse per row",
+     "GPU*", "top-level fields as columns `c0, c1, ...`; each name is a "
+     "literal key, never a path; SQL `json_tuple(j, 'a', 'b') [AS (x, y)]` "
+     "in a select list, no `LATERAL VIEW`; otherwise as GetJsonObject"),
     ("Murmur3Hash", "k_murmur3", "GPU", "spark-exact, seeds chain"),
     # datetime
     ("Year", "UnaryExpr year", "GPU", "civil calendar kernel"),
