@@ -527,4 +527,7 @@ PYBIND11_MODULE(hipdf, m) {
   BIND(list_union_map);
   BIND(list_elem_rows);
   BIND(list_bool_reduce);
+  BIND(list_find);
+  BIND(list_slice_ranges);
+  BIND(list_slice_map);
 }

@@ -718,6 +718,41 @@ void hipdf_list_bool_reduce(const void* pred, const void* pvalid,
                             const void* offsets, const void* rvalid, int w,
                             int mode, void* out, void* vout, int64_t n,
                             hipStream_t stream);
+/* Per-row search of a LIST of n rows for the row's own needle, w lanes
+ * (8/16/32/64) per row. t / data / eoffs / cvalid / offsets / rvalid describe
+ * the list as above; ndata / neoffs / nvalid are a column of the element type
+ * with one needle per row (nvalid may be NULL). A row is live when it and its
+ * needle are non-null; other rows are not read through. An element matches
+ * when it is non-null and equals the needle (NaN equals NaN, -0.0 equals 0.0,
+ * strings by bytes). Each output may be NULL when not wanted.
+ * match: uint8[offsets[n] - offsets[0]], 1 at a match, 0 all over a row that
+ * is not live; first: int64[n], 1-based place of the first match, 0 for none;
+ * vout: validity words covering n rows, every word written whole, bit = live */
+void hipdf_list_find(int t, const void* data, const void* eoffs,
+                     const void* cvalid, const void* offsets,
+                     const void* rvalid, const void* ndata,
+                     const void* neoffs, const void* nvalid, int w,
+                     void* match, void* first, void* vout, int64_t n,
+                     hipStream_t stream);
+/* slice(list, start, length) per row; start and length are int32[n] columns
+ * with their validity (each may be NULL). A row is live when all three are
+ * non-null. start is 1-based, a negative start counts from the end, a first
+ * element outside the row gives an empty result; the arithmetic is 64-bit.
+ * src_start: int32[n], global child index of the first element taken;
+ * out_len: int64[n + 1], elements taken (0 for a row that is not live or is
+ * in error), entry n is 0; vout: validity words covering n rows, bit = live;
+ * err: uint64[2], zeroed by the caller: live rows with start == 0, live rows
+ * with length < 0 are added to it */
+void hipdf_list_slice_ranges(const void* offsets, const void* rvalid,
+                             const void* start, const void* svalid,
+                             const void* length, const void* lvalid,
+                             void* src_start, void* out_len, void* vout,
+                             void* err, int64_t n, hipStream_t stream);
+/* gather map of slice, one thread per output element: new_offs int32[n + 1]
+ * from 0 to total; idx[p] = src_start[row] + (p - new_offs[row]) */
+void hipdf_list_slice_map(const void* new_offs, const void* src_start,
+                          int64_t n, void* idx, int64_t total,
+                          hipStream_t stream);
 
 /* ---- device memory pool (pool.hip) ------------------------------------- */
 /* reserve `bytes` (or fraction of free memory if bytes==0) as the pool

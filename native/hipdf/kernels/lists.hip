@@ -558,6 +558,142 @@ __global__ __launch_bounds__(HIPDF_BLOCK) void k_list_bool_reduce(
   }
 }
 
+// ---- search, slice -------------------------------------------------------
+// array_position / array_remove / slice (reference analogue:
+// GpuArrayPosition, GpuArrayRemove, GpuSlice in collectionOperations.scala).
+// Next to the list each row has a scalar operand: the needle, or the start
+// and the length.
+
+// Per-row search for the row's needle (entry `row` of a second source of the
+// same kind). An element matches when it is non-null and equal to the needle
+// under k_list_member_flags's equality: equal key() and a zero tie(). A row
+// is live when it and its needle are non-null; only live rows are read
+// through. match (one entry per element from offsets[0]) is 0 all over a row
+// that is not live; first is the 1-based place of the first match, 0 for
+// none. Any of the three outputs may be null. Stripes, W and the word write
+// are k_list_bool_reduce's; rows longer than W are covered by the stride.
+template <typename Src, int W>
+__global__ __launch_bounds__(HIPDF_BLOCK) void k_list_find(
+    Src src, const uint64_t* __restrict__ cvalid,
+    const int32_t* __restrict__ offsets, const uint64_t* __restrict__ rvalid,
+    Src needle, const uint64_t* __restrict__ nvalid,
+    uint8_t* __restrict__ match, int64_t* __restrict__ first,
+    uint64_t* __restrict__ vout, int64_t n) {
+  constexpr int L = WAVE / W;  // rows per step
+  constexpr int32_t NONE = 0x7fffffff;
+  int lane = lane_id();
+  int sub = lane / W, sl = lane & (W - 1);
+  int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  int64_t nwaves = (int64_t)gridDim.x * blockDim.x / WAVE;
+  int64_t nstripes = (n + WAVE - 1) / WAVE;
+  int32_t off0 = offsets[0];
+  // loop bounds are wave-uniform: every lane reaches every shuffle / ballot
+  for (int64_t stripe = wave; stripe < nstripes; stripe += nwaves) {
+    uint64_t word = 0;
+    for (int step = 0; step < W; ++step) {
+      int64_t row = stripe * WAVE + step * L + sub;
+      bool live = row < n && valid_bit(rvalid, row) && valid_bit(nvalid, row);
+      int32_t start = 0, len = 0;
+      if (row < n && (live || match)) {
+        start = offsets[row];
+        len = offsets[row + 1] - start;
+      }
+      uint64_t nk = live ? needle.key((int32_t)row) : 0;
+      int32_t best = NONE;
+      // the element loop has no shuffle in it, so its bounds may differ
+      for (int32_t i = sl; i < len; i += W) {
+        int32_t gi = start + i;
+        bool hit = live && valid_bit(cvalid, gi) && src.key(gi) == nk &&
+                   src.tie(gi, needle, (int32_t)row) == 0;
+        if (match) match[gi - off0] = hit ? 1 : 0;
+        if (hit && best == NONE) {
+          best = i;
+          if (!match) break;  // later elements of this lane come after it
+        }
+      }
+#pragma unroll
+      for (int j = W >> 1; j > 0; j >>= 1) {
+        int32_t o = __shfl_xor(best, j, W);
+        best = o < best ? o : best;
+      }
+      uint64_t bal = __ballot(live && sl == 0);  // bit sub * W = row's bit
+#pragma unroll
+      for (int g = 0; g < L; ++g)
+        word |= ((bal >> (g * W)) & 1ull) << (step * L + g);
+      if (first && sl == 0 && row < n)
+        first[row] = best == NONE ? 0 : (int64_t)best + 1;
+    }
+    if (vout && lane == 0) vout[stripe] = word;
+  }
+}
+
+// slice(a, start, length) per row, one lane per row and one wave per 64-row
+// stripe. A row is live when it, its start and its length are non-null.
+// start is 1-based, negative counts from the end; everything is 64-bit, so
+// start + length cannot wrap. src_start: global child index of the first
+// element taken; out_len: elements taken, 0 for a row that is not live, is
+// empty or is in error, and entry n is 0 so that the array scans into n + 1
+// offsets. err[0] counts live rows with start == 0, err[1] those with
+// length < 0 (the host zeroes err and raises).
+__global__ __launch_bounds__(HIPDF_BLOCK) void k_list_slice_ranges(
+    const int32_t* __restrict__ offsets, const uint64_t* __restrict__ rvalid,
+    const int32_t* __restrict__ start, const uint64_t* __restrict__ svalid,
+    const int32_t* __restrict__ length, const uint64_t* __restrict__ lvalid,
+    int32_t* __restrict__ src_start, int64_t* __restrict__ out_len,
+    uint64_t* __restrict__ vout, unsigned long long* __restrict__ err,
+    int64_t n) {
+  int lane = lane_id();
+  int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  int64_t nwaves = (int64_t)gridDim.x * blockDim.x / WAVE;
+  // rows 0..n: the last stripe also holds the closing entry of out_len
+  int64_t nstripes = (n + 1 + WAVE - 1) / WAVE;
+  for (int64_t stripe = wave; stripe < nstripes; stripe += nwaves) {
+    int64_t row = stripe * WAVE + lane;
+    bool live = row < n && valid_bit(rvalid, row) && valid_bit(svalid, row) &&
+                valid_bit(lvalid, row);
+    int32_t s0 = 0;
+    int64_t taken = 0;
+    bool bad_start = false, bad_len = false;
+    if (live) {
+      int64_t st = start[row], ln = length[row];
+      int32_t b = offsets[row];
+      int64_t len = (int64_t)offsets[row + 1] - b;
+      bad_start = st == 0;
+      bad_len = ln < 0;
+      if (!bad_start && !bad_len) {
+        int64_t f = st > 0 ? st - 1 : len + st;
+        if (f >= 0 && f < len) {
+          int64_t e = f + ln < len ? f + ln : len;
+          s0 = b + (int32_t)f;
+          taken = e - f;
+        }
+      }
+    }
+    if (row < n) src_start[row] = s0;
+    if (row <= n) out_len[row] = taken;
+    uint64_t bal = __ballot(live);
+    uint64_t bs = __ballot(bad_start), bl = __ballot(bad_len);
+    if (lane == 0) {
+      if (stripe * WAVE < n) vout[stripe] = bal;
+      if (bs) atomicAdd(&err[0], (unsigned long long)__popcll(bs));
+      if (bl) atomicAdd(&err[1], (unsigned long long)__popcll(bl));
+    }
+  }
+}
+
+// gather map of slice: idx[p] = src_start[row] + (p - new_offs[row]) for the
+// row that owns output element p; new_offs are the result's offsets, from 0.
+__global__ void k_list_slice_map(const int32_t* __restrict__ new_offs,
+                                 const int32_t* __restrict__ src_start,
+                                 int64_t n, int32_t* __restrict__ idx,
+                                 int64_t total) {
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total;
+       p += (int64_t)gridDim.x * blockDim.x) {
+    int64_t row = row_of(new_offs, n, (int32_t)p);
+    idx[p] = src_start[row] + ((int32_t)p - new_offs[row]);
+  }
+}
+
 // ---- host side -----------------------------------------------------------
 
 template <typename F>
@@ -728,6 +864,51 @@ void hipdf_list_bool_reduce(const void* pred, const void* pvalid,
                        (const uint64_t*)rvalid, mode == 0 ? 1 : 0,
                        (uint8_t*)out, (uint64_t*)vout, n);
   });
+}
+
+void hipdf_list_find(int t, const void* data, const void* eoffs,
+                     const void* cvalid, const void* offsets,
+                     const void* rvalid, const void* ndata,
+                     const void* neoffs, const void* nvalid, int w,
+                     void* match, void* first, void* vout, int64_t n,
+                     hipStream_t stream) {
+  if (n <= 0) return;
+  int64_t waves = (n + WAVE - 1) / WAVE;  // one wave per 64-row stripe
+  dispatch_src(t, data, eoffs, [&](auto src) {
+    using Src = decltype(src);
+    dispatch_width(w, [&]<int W>() {
+      hipLaunchKernelGGL((k_list_find<Src, W>), flat_grid(waves * WAVE),
+                         dim3(HIPDF_BLOCK), 0, stream, src,
+                         (const uint64_t*)cvalid, (const int32_t*)offsets,
+                         (const uint64_t*)rvalid, Src::of(ndata, neoffs),
+                         (const uint64_t*)nvalid, (uint8_t*)match,
+                         (int64_t*)first, (uint64_t*)vout, n);
+    });
+  });
+}
+
+void hipdf_list_slice_ranges(const void* offsets, const void* rvalid,
+                             const void* start, const void* svalid,
+                             const void* length, const void* lvalid,
+                             void* src_start, void* out_len, void* vout,
+                             void* err, int64_t n, hipStream_t stream) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_list_slice_ranges, stripe_grid(n + 1),
+                     dim3(HIPDF_BLOCK), 0, stream, (const int32_t*)offsets,
+                     (const uint64_t*)rvalid, (const int32_t*)start,
+                     (const uint64_t*)svalid, (const int32_t*)length,
+                     (const uint64_t*)lvalid, (int32_t*)src_start,
+                     (int64_t*)out_len, (uint64_t*)vout,
+                     (unsigned long long*)err, n);
+}
+
+void hipdf_list_slice_map(const void* new_offs, const void* src_start,
+                          int64_t n, void* idx, int64_t total,
+                          hipStream_t stream) {
+  if (n <= 0 || total <= 0) return;
+  hipLaunchKernelGGL(k_list_slice_map, flat_grid(total), dim3(HIPDF_BLOCK), 0,
+                     stream, (const int32_t*)new_offs,
+                     (const int32_t*)src_start, n, (int32_t*)idx, total);
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@ on the CPU backend or on the GPU backend depending on where the batch lives.
 """
 from __future__ import annotations
 
+import decimal
 import inspect
 import itertools
 from typing import Optional, Sequence
@@ -211,6 +212,22 @@ class Expression:
         when they share none, both are non-empty and either holds a null,
         else false (Spark arrays_overlap)."""
         return ArraysOverlap(self, other)
+
+    def array_position(self, value) -> "ArrayPosition":
+        """1-based place of the first element of this LIST value equal to
+        `value` (an expression of the element type or a python scalar), 0
+        when there is none (Spark array_position)."""
+        return ArrayPosition(self, value)
+
+    def array_remove(self, value) -> "ArrayRemove":
+        """This LIST value without every element equal to `value`; null
+        elements stay (Spark array_remove)."""
+        return ArrayRemove(self, value)
+
+    def slice(self, start, length) -> "ArraySlice":
+        """At most `length` elements of this LIST value from the 1-based
+        `start`; a negative start counts from the end (Spark slice)."""
+        return ArraySlice(self, start, length)
 
     def transform(self, f) -> "ArrayTransform":
         """Apply `f` to every element of a LIST value (Spark transform).
@@ -952,6 +969,216 @@ class ArraysOverlap(_ArraySetOp):
         return DType.bool_()
 
 
+def _decimal_needle(fn: str, v, et: DType) -> decimal.Decimal:
+    """An int, float or Decimal scalar as the Decimal VALUE it stands for,
+    which Column.full then scales: 5 against decimal(12, 2) is 5.00, never
+    the unscaled 0.05. There is no widening here either: a value that
+    decimal(p, s) cannot hold exactly is a TypeError, not a needle that
+    matches nothing."""
+    ctx = decimal.Context(prec=60)
+    d = decimal.Decimal(repr(v)) if isinstance(v, float) \
+        else decimal.Decimal(v)
+    ok = d.is_finite()
+    if ok:
+        unscaled = d.scaleb(et.scale, ctx)
+        ok = unscaled == unscaled.to_integral_value() and \
+            abs(unscaled) < 10 ** et.precision
+    if not ok:
+        raise TypeError(f"{fn}: the value {v!r} cannot be held exactly by "
+                        f"elements of type {et}")
+    return d
+
+
+def _needle_literal(fn: str, v, et: DType) -> Literal:
+    """A python scalar as a Literal of the element type `et`, coerced by
+    value the way _coerce_py does it (an int widens to a floating element
+    type; an int, a float or a Decimal stands for its value against a
+    decimal one); a scalar of another kind is a TypeError."""
+    if v is None:
+        return Literal(None, et)
+    if isinstance(v, bool):
+        ok = et.id is TypeId.BOOL
+    elif isinstance(v, int):
+        ok = et.id is not TypeId.BOOL and (
+            et.is_integral or et.is_floating or et.is_decimal
+            or et.id in (TypeId.DATE32, TypeId.TIMESTAMP))
+    elif isinstance(v, float):
+        ok = et.is_floating or et.is_decimal
+    elif isinstance(v, str):
+        ok = et.id is TypeId.STRING
+    elif isinstance(v, decimal.Decimal):
+        ok = et.is_decimal
+    else:
+        ok = False
+    if not ok:
+        raise TypeError(f"{fn}: the {type(v).__name__} value {v!r} cannot be "
+                        f"compared with elements of type {et}")
+    if et.is_decimal:
+        return Literal(_decimal_needle(fn, v, et), et)
+    return Literal(_coerce_py(v, et), et)
+
+
+class _ArrayNeedleFn(Expression):
+    """A LIST value and a value `v` of exactly its element type, one per
+    row: a column, a typed literal or a computed expression (no implicit
+    widening, as with the set operations). Only a python scalar is coerced
+    to the element type, by value; `lit(None)` is a null needle. Element
+    equality is array_distinct's, except that a null element equals
+    nothing. A row is NULL when the array or `v` is."""
+
+    fn = ""
+
+    def __init__(self, child: Expression, value):
+        self.child = child
+        self.value = value  # an Expression, or the python scalar as given
+
+    @property
+    def children(self):
+        if isinstance(self.value, Expression):
+            return (self.child, self.value)
+        return (self.child,)
+
+    def _needle(self, schema: Schema) -> Expression:
+        cdt = self.child.dtype(schema)
+        if cdt.id is not TypeId.LIST:
+            raise TypeError(f"{self.fn} needs an array input, got {cdt}")
+        et = cdt.children[0]
+        v = self.value
+        if not isinstance(v, Expression):
+            return _needle_literal(self.fn, v, et)
+        vt = v.dtype(schema)
+        if vt.id is TypeId.NULL and isinstance(v, Literal):
+            return Literal(None, et)
+        if vt != et:
+            raise TypeError(f"{self.fn} needs a value of the array's element "
+                            f"type, got {cdt} and {vt}")
+        return v
+
+    def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
+        needle = self._needle(schema)
+        return getattr(ops, self.fn)(self.child.eval(batch, schema),
+                                     needle.eval(batch, schema))
+
+    def __str__(self):
+        v = self.value
+        return f"{self.fn}({self.child}, " \
+               f"{v if isinstance(v, Expression) else repr(v)})"
+
+
+class ArrayPosition(_ArrayNeedleFn):
+    """array_position(a, v): INT64 1-based place of the first element equal
+    to v, 0 when there is none (GpuArrayPosition analogue)."""
+
+    fn = "array_position"
+
+    def dtype(self, schema: Schema) -> DType:
+        self._needle(schema)
+        return INT64
+
+
+class ArrayRemove(_ArrayNeedleFn):
+    """array_remove(a, v): a without every element equal to v; order, null
+    elements and bit patterns are kept (GpuArrayRemove analogue)."""
+
+    fn = "array_remove"
+
+    def dtype(self, schema: Schema) -> DType:
+        self._needle(schema)
+        return self.child.dtype(schema)
+
+
+def _int32_operand(fn: str, what: str, v) -> Expression:
+    if isinstance(v, bool) or not isinstance(v, (int, Expression)):
+        raise TypeError(f"{fn}: {what} must be an int or an integer "
+                        f"expression, got {type(v).__name__}")
+    if isinstance(v, int):
+        if not -(2 ** 31) <= v < 2 ** 31:
+            raise ValueError(f"{fn}: {what} {v} is outside the INT32 range")
+        return Literal(v, INT32)
+    return v
+
+
+def _as_int32(fn: str, what: str, e: Expression, schema: Schema) -> Expression:
+    """`e` cast to INT32 with the engine's CastExpr; integer types only."""
+    t = e.dtype(schema)
+    if isinstance(e, Literal) and e.value is None:
+        return Literal(None, INT32)
+    if not t.is_integral or t.id is TypeId.BOOL:
+        raise TypeError(f"{fn}: {what} must be an integer, got {t}")
+    return e if t == INT32 else CastExpr(e, INT32)
+
+
+class ArraySlice(Expression):
+    """slice(a, start, length): the elements from the 1-based `start` (a
+    negative one counts from the end), at most `length` of them; an empty
+    array when the start falls outside the row. start and length are
+    python ints or integer expressions, cast to INT32. NULL when any of the
+    three is; start == 0 or length < 0 in a row where none is raises
+    ValueError (GpuSlice analogue)."""
+
+    def __init__(self, child: Expression, start, length):
+        self.child = child
+        self.start = _int32_operand("slice", "start", start)
+        self.length = _int32_operand("slice", "length", length)
+
+    @property
+    def children(self):
+        return (self.child, self.start, self.length)
+
+    def _operands(self, schema: Schema):
+        cdt = self.child.dtype(schema)
+        if cdt.id is not TypeId.LIST:
+            raise TypeError(f"slice needs an array input, got {cdt}")
+        return (_as_int32("slice", "start", self.start, schema),
+                _as_int32("slice", "length", self.length, schema))
+
+    def dtype(self, schema: Schema) -> DType:
+        self._operands(schema)
+        return self.child.dtype(schema)
+
+    def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
+        start, length = self._operands(schema)
+        return ops.array_slice(self.child.eval(batch, schema),
+                               start.eval(batch, schema),
+                               length.eval(batch, schema))
+
+    def __str__(self):
+        return f"slice({self.child}, {self.start}, {self.length})"
+
+
+class ArrayRepeat(Expression):
+    """array_repeat(e, n): an array of n copies of e; empty for n <= 0, NULL
+    for a null n, an array of nulls for a null e. n is a python int or an
+    integer expression, cast to INT32 (GpuArrayRepeat analogue)."""
+
+    def __init__(self, child, count):
+        self.child = _as_expr(child)
+        self.count = _int32_operand("array_repeat", "count", count)
+
+    @property
+    def children(self):
+        return (self.child, self.count)
+
+    def _count(self, schema: Schema) -> Expression:
+        return _as_int32("array_repeat", "count", self.count, schema)
+
+    def dtype(self, schema: Schema) -> DType:
+        self._count(schema)
+        et = self.child.dtype(schema)
+        if et.id is TypeId.NULL:
+            raise TypeError("array_repeat needs a typed element; cast the "
+                            "NULL literal")
+        return DType.list_(et)
+
+    def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
+        self.dtype(schema)
+        return ops.array_repeat(self.child.eval(batch, schema),
+                                self._count(schema).eval(batch, schema))
+
+    def __str__(self):
+        return f"array_repeat({self.child}, {self.count})"
+
+
 _lambda_ids = itertools.count()
 
 
@@ -1223,6 +1450,23 @@ def exists(a, f) -> ArrayExists:
 
 def forall(a, f) -> ArrayForAll:
     return _as_expr(a).forall(f)
+
+
+def array_position(a, v) -> ArrayPosition:
+    return _as_expr(a).array_position(v)
+
+
+def array_remove(a, v) -> ArrayRemove:
+    return _as_expr(a).array_remove(v)
+
+
+def slice_(a, start, length) -> ArraySlice:
+    """slice(a, start, length); the underscore keeps python's slice."""
+    return _as_expr(a).slice(start, length)
+
+
+def array_repeat(e, count) -> ArrayRepeat:
+    return ArrayRepeat(e, count)
 
 
 class HostStringFn(Expression):

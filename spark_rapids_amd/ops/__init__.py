@@ -108,6 +108,37 @@ def arrays_overlap(a: Column, b: Column) -> Column:
     return backend_for(a, b).arrays_overlap(a, b)
 
 
+def array_position(col: Column, needle: Column) -> Column:
+    """INT64 1-based place of the first element equal to the row's entry of
+    `needle` (a column of the element type), 0 when there is none; NULL
+    when the row or the needle is. Equality is array_distinct's, and a null
+    element equals nothing (GpuArrayPosition analogue)."""
+    return backend_for(col, needle).array_position(col, needle)
+
+
+def array_remove(col: Column, needle: Column) -> Column:
+    """The array without every element equal to the row's needle; order,
+    null elements and bit patterns are kept; NULL when the row or the
+    needle is (GpuArrayRemove analogue)."""
+    return backend_for(col, needle).array_remove(col, needle)
+
+
+def array_slice(col: Column, start: Column, length: Column) -> Column:
+    """slice(array, start, length) with INT32 start and length columns:
+    1-based start, negative from the end, an empty array when it falls
+    outside the row; NULL when any of the three is. start == 0 or
+    length < 0 in a row where none is null raises ValueError with Spark's
+    text (GpuSlice analogue)."""
+    return backend_for(col, start, length).array_slice(col, start, length)
+
+
+def array_repeat(elem: Column, count: Column) -> Column:
+    """LIST of `count` (INT32) copies of the row's element: empty for
+    count <= 0, NULL for a null count, nulls for a null element
+    (GpuArrayRepeat analogue)."""
+    return backend_for(elem, count).array_repeat(elem, count)
+
+
 def list_span(col: Column) -> Tuple[int, int]:
     """(offsets[0], offsets[n] - offsets[0]) of a LIST column: where its
     elements start in the child and how many there are. The one host read

@@ -820,6 +820,98 @@ def arrays_overlap(a: Column, b: Column) -> Column:
     return Column.from_pylist(out, DType.bool_())
 
 
+def _array_needle_rows(fn: str, col: Column, needle: Column):
+    if col.dtype.id is not TypeId.LIST or needle.dtype != col.dtype.children[0]:
+        raise TypeError(f"{fn} needs an array and a value of its element "
+                        f"type, got {col.dtype} and {needle.dtype}")
+    if needle.size != col.size:
+        raise ValueError(f"{fn}: {col.size} arrays and {needle.size} values")
+    return zip(col.to_pylist(), needle.to_pylist())
+
+
+def _elem_equals(x, key) -> bool:
+    """A null element equals no needle."""
+    return x is not None and _array_elem_key(x) == key
+
+
+def array_position(col: Column, needle: Column) -> Column:
+    """1-based place of the first element equal to the row's needle, 0 when
+    there is none; NULL when the row or the needle is."""
+    out = []
+    for v, x in _array_needle_rows("array_position", col, needle):
+        if v is None or x is None:
+            out.append(None)
+            continue
+        k = _array_elem_key(x)
+        out.append(next((i + 1 for i, e in enumerate(v)
+                         if _elem_equals(e, k)), 0))
+    return Column.from_pylist(out, DType.int64())
+
+
+def array_remove(col: Column, needle: Column) -> Column:
+    """The array without the elements equal to the row's needle; order and
+    null elements are kept. NULL when the row or the needle is."""
+    out = []
+    for v, x in _array_needle_rows("array_remove", col, needle):
+        if v is None or x is None:
+            out.append(None)
+            continue
+        k = _array_elem_key(x)
+        out.append([e for e in v if not _elem_equals(e, k)])
+    return Column.from_pylist(out, col.dtype)
+
+
+SLICE_START_ERROR = ("Unexpected value for start in function slice: "
+                     "SQL array indices start at 1.")
+SLICE_LENGTH_ERROR = ("Unexpected value for length in function slice: "
+                      "length must be greater than or equal to 0.")
+
+
+def _int32_operand_rows(fn: str, what: str, c: Column, n: int) -> list:
+    if c.dtype.id is not TypeId.INT32:
+        raise TypeError(f"{fn}: {what} must be INT32, got {c.dtype}")
+    if c.size != n:
+        raise ValueError(f"{fn}: {n} rows and {c.size} {what} values")
+    return c.to_pylist()
+
+
+def array_slice(col: Column, start: Column, length: Column) -> Column:
+    """slice(array, start, length): 1-based start, a negative one counts
+    from the end, a first element outside the row gives an empty array.
+    NULL when any operand is; a zero start or a negative length raises
+    only in a row where none is, start before length over the column."""
+    if col.dtype.id is not TypeId.LIST:
+        raise TypeError(f"slice needs an array input, got {col.dtype}")
+    n = col.size
+    rows = list(zip(col.to_pylist(),
+                    _int32_operand_rows("slice", "start", start, n),
+                    _int32_operand_rows("slice", "length", length, n)))
+    live = [r for r in rows if None not in r]
+    if any(s == 0 for _, s, _ in live):
+        raise ValueError(SLICE_START_ERROR)
+    if any(ln < 0 for _, _, ln in live):
+        raise ValueError(SLICE_LENGTH_ERROR)
+    out = []
+    for v, s, ln in rows:
+        if v is None or s is None or ln is None:
+            out.append(None)
+            continue
+        first = s - 1 if s > 0 else len(v) + s  # python ints: no wrap
+        out.append(v[first:first + ln] if 0 <= first < len(v) else [])
+    return Column.from_pylist(out, col.dtype)
+
+
+def array_repeat(elem: Column, count: Column) -> Column:
+    """count copies of the row's element (nulls for a null element), an
+    empty array for count <= 0, NULL for a null count."""
+    counts = _int32_operand_rows("array_repeat", "count", count, elem.size)
+    if sum(max(c, 0) for c in counts if c is not None) > 2 ** 31 - 1:
+        raise OverflowError("array_repeat result exceeds int32 offsets")
+    out = [None if c is None else [e] * max(c, 0)
+           for e, c in zip(elem.to_pylist(), counts)]
+    return Column.from_pylist(out, DType.list_(elem.dtype))
+
+
 def list_span(col: Column):
     """(first offset, child rows covered)."""
     n = col.size

@@ -17,6 +17,7 @@ import torch
 
 from ..column import Column, ColumnBatch, mask_nbytes, torch_dtype
 from ..types import DType, TypeId
+from .cpu_backend import SLICE_LENGTH_ERROR, SLICE_START_ERROR
 
 import importlib
 
@@ -1383,6 +1384,157 @@ def array_forall(col: Column, pred: Column, span=None) -> Column:
     return _list_bool_reduce(col, pred, 1, span)
 
 
+# search, slice, repeat: a per-row scalar operand next to the array
+
+def _list_needle_check(fn: str, col: Column, needle: Column) -> None:
+    if col.dtype.id is not TypeId.LIST or needle.dtype != col.dtype.children[0]:
+        raise TypeError(f"{fn} needs an array and a value of its element "
+                        f"type, got {col.dtype} and {needle.dtype}")
+    if needle.size != col.size:
+        raise ValueError(f"{fn}: {col.size} arrays and {needle.size} values")
+
+
+def _list_find(col: Column, needle: Column, total: int, want_match: bool,
+               want_first: bool):
+    """(match uint8[total] or None, first int64[n] or None, validity of
+    row AND needle) from one list_find launch; n > 0 and total > 0."""
+    n = col.size
+    t, dp, eo = _list_elem_args(col.child)
+    _, ndp, neo = _list_elem_args(needle)
+    match = torch.empty(total, dtype=torch.uint8, device="cuda") \
+        if want_match else None
+    first = torch.empty(n, dtype=torch.int64, device="cuda") \
+        if want_first else None
+    ov = _alloc_mask(n)
+    # lanes per row from the mean length, as list_bool_reduce
+    ext.list_find(t, dp, eo, _ptr(col.child.validity), col.offsets.data_ptr(),
+                  _ptr(col.validity), ndp, neo, _ptr(needle.validity),
+                  _list_group_width(-(-total // n)), _ptr(match), _ptr(first),
+                  ov.data_ptr(), n, _stream())
+    return match, first, ov
+
+
+def array_position(col: Column, needle: Column) -> Column:
+    """1-based place of the first element equal to the row's needle, 0 for
+    none; NULL when the row or the needle is (list_find)."""
+    _list_needle_check("array_position", col, needle)
+    n = col.size
+    if n == 0:
+        return _empty_col(DType.int64())
+    _, total = list_span(col)
+    if total == 0:  # every row is empty or null
+        v = _and_masks(col.validity, needle.validity)
+        return Column(DType.int64(), n,
+                      torch.zeros(n, dtype=torch.int64, device="cuda"), v,
+                      null_count=None if v is not None else 0)
+    _, first, ov = _list_find(col, needle, total, False, True)
+    return Column(DType.int64(), n, first, ov, null_count=None)
+
+
+def array_remove(col: Column, needle: Column) -> Column:
+    """The array without the elements equal to the row's needle, order and
+    null elements kept; NULL when the row or the needle is. list_find's
+    match flags, negated, go through array_distinct's compaction."""
+    _list_needle_check("array_remove", col, needle)
+    n = col.size
+    if n == 0:
+        return Column.from_pylist([], col.dtype).cuda()
+    off0, total = list_span(col)
+    empty = torch.zeros(0, dtype=torch.uint8, device="cuda")
+    if total == 0:
+        v = _and_masks(col.validity, needle.validity)
+        return Column(col.dtype, n, empty, v, _list_rebased_offsets(col, off0),
+                      None if v is not None else 0,
+                      _empty_col(col.child.dtype))
+    match, _, ov = _list_find(col, needle, total, True, False)
+    keep = unary_op("not", _flag_col(match), DType.bool_()).data
+    new_offs, child = _list_compact(col, keep, off0, total)
+    return Column(col.dtype, n, empty, ov, new_offs, None, child)
+
+
+def _int32_operand(fn: str, what: str, c: Column, n: int) -> Column:
+    if c.dtype.id is not TypeId.INT32:
+        raise TypeError(f"{fn}: {what} must be INT32, got {c.dtype}")
+    if c.size != n:
+        raise ValueError(f"{fn}: {n} rows and {c.size} {what} values")
+    return c
+
+
+def array_slice(col: Column, start: Column, length: Column) -> Column:
+    """slice(array, start, length): list_slice_ranges turns the three
+    operands into a first child index and a length per row, the lengths
+    scan into the new offsets, list_slice_map writes the gather map."""
+    if col.dtype.id is not TypeId.LIST:
+        raise TypeError(f"slice needs an array input, got {col.dtype}")
+    n = col.size
+    s = _stream()
+    _int32_operand("slice", "start", start, n)
+    _int32_operand("slice", "length", length, n)
+    if n == 0:
+        return Column.from_pylist([], col.dtype).cuda()
+    src_start = torch.empty(n, dtype=torch.int32, device="cuda")
+    out_len = torch.empty(n + 1, dtype=torch.int64, device="cuda")
+    ov = _alloc_mask(n)
+    err = torch.zeros(2, dtype=torch.int64, device="cuda")
+    ext.list_slice_ranges(col.offsets.data_ptr(), _ptr(col.validity),
+                          start.data.data_ptr(), _ptr(start.validity),
+                          length.data.data_ptr(), _ptr(length.validity),
+                          src_start.data_ptr(), out_len.data_ptr(),
+                          ov.data_ptr(), err.data_ptr(), n, s)
+    # the error record comes back with the scan total, one blocking read
+    scanned, total, (bad_start, bad_len) = _exclusive_scan_i64(out_len, err)
+    if bad_start:
+        raise ValueError(SLICE_START_ERROR)
+    if bad_len:
+        raise ValueError(SLICE_LENGTH_ERROR)
+    new_offs = torch.empty(n + 1, dtype=torch.int32, device="cuda")
+    ext.narrow_i64_i32(scanned.data_ptr(), new_offs.data_ptr(), n + 1, s)
+    if total:
+        idx = torch.empty(total, dtype=torch.int32, device="cuda")
+        ext.list_slice_map(new_offs.data_ptr(), src_start.data_ptr(), n,
+                           idx.data_ptr(), total, s)
+        child = _gather_col(col.child, idx, total, maybe_negative=False)
+    else:
+        child = _empty_col(col.child.dtype)
+    return Column(col.dtype, n, torch.zeros(0, dtype=torch.uint8,
+                                            device="cuda"),
+                  ov, new_offs, None, child)
+
+
+def array_repeat(elem: Column, count: Column) -> Column:
+    """count copies of the row's element (a null element gives nulls), no
+    copies for count <= 0, NULL for a null count. The lengths scan into
+    the offsets; the element-to-row map over them is the gather map."""
+    n = elem.size
+    s = _stream()
+    _int32_operand("array_repeat", "count", count, n)
+    dtype = DType.list_(elem.dtype)
+    if n == 0:
+        return Column.from_pylist([], dtype).cuda()
+    lens = binary_op_scalar("max", count, 0, DType.int32())
+    if count.validity is not None:
+        present = unary_op("not", is_null(count), DType.bool_())
+        lens = if_else(present, lens, Column.full(0, DType.int32(), n, "cuda"))
+    lens64 = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+    ext.cast(_ht(DType.int32()), _ht(DType.int64()), lens.data.data_ptr(),
+             lens64.data_ptr(), n, s)
+    scanned, total = _exclusive_scan_i64(lens64)
+    if total > 2 ** 31 - 1:
+        raise OverflowError("array_repeat result exceeds int32 offsets")
+    new_offs = torch.empty(n + 1, dtype=torch.int32, device="cuda")
+    ext.narrow_i64_i32(scanned.data_ptr(), new_offs.data_ptr(), n + 1, s)
+    if total:
+        rowid = torch.empty(total, dtype=torch.int32, device="cuda")
+        ext.list_elem_rows(new_offs.data_ptr(), n, rowid.data_ptr(), 0, total,
+                           s)
+        child = _gather_col(elem, rowid, total, maybe_negative=False)
+    else:
+        child = _empty_col(elem.dtype)
+    v = count.validity.clone() if count.validity is not None else None
+    return Column(dtype, n, torch.zeros(0, dtype=torch.uint8, device="cuda"),
+                  v, new_offs, count._null_count, child)
+
+
 def _array_extreme(col: Column, is_max: bool) -> Column:
     n = col.size
     s = _stream()
@@ -1722,19 +1874,25 @@ def if_else(cond: Column, a: Column, b: Column) -> Column:
 # scan helper
 # ---------------------------------------------------------------------------
 
-def _exclusive_scan_i64(vals: torch.Tensor) -> Tuple[torch.Tensor, int]:
-    """Returns (exclusive scan tensor, total)."""
+def _exclusive_scan_i64(vals: torch.Tensor,
+                        also: Optional[torch.Tensor] = None):
+    """Returns (exclusive scan tensor, total). `also`, a small int64 device
+    tensor, rides along in the one blocking readback of the total and comes
+    back as a third item, a list."""
     n = vals.numel()
     s = _stream()
     if n == 0:
-        return vals, 0
+        return (vals, 0) if also is None else (vals, 0, also.tolist())
     out = torch.empty(n, dtype=torch.int64, device="cuda")
     scratch = torch.empty(ext.scan_scratch_elems(n), dtype=torch.int64,
                           device="cuda")
     # every level in one native call; the grand total is scratch's last slot
     ext.exclusive_scan_i64(vals.data_ptr(), out.data_ptr(),
                            scratch.data_ptr(), n, s)
-    return out, int(scratch[-1].item())
+    if also is None:
+        return out, int(scratch[-1].item())
+    host = torch.cat([scratch[-1:], also]).tolist()
+    return out, int(host[0]), host[1:]
 
 
 # ---------------------------------------------------------------------------

@@ -71,6 +71,9 @@ _ARRAY_FN_NAMES = {"SortArray": "sort_array", "ArraySort": "array_sort",
                    "ArraysOverlap": "arrays_overlap"}
 _ARRAY_SET_OPS = ("ArrayUnion", "ArrayIntersect", "ArrayExcept",
                   "ArraysOverlap")
+_ARRAY_SEARCH_FNS = {"ArrayPosition": "array_position",
+                     "ArrayRemove": "array_remove", "ArraySlice": "slice",
+                     "ArrayRepeat": "array_repeat"}
 _ARRAY_LAMBDAS = ("ArrayTransform", "ArrayFilter", "ArrayExists",
                   "ArrayForAll")
 
@@ -189,6 +192,8 @@ class Tagger:
                     out.append(f"{fn} over decimal128 elements on CPU")
                 elif not (et.is_fixed_width or et.id is TypeId.STRING):
                     out.append(f"{fn} over {et} elements on CPU")
+        elif type(e).__name__ in _ARRAY_SEARCH_FNS:
+            self._tag_array_search(e, schema, out)
         elif type(e).__name__ == "LambdaVariable":
             pass
         elif type(e).__name__ in _ARRAY_LAMBDAS:
@@ -233,6 +238,27 @@ class Tagger:
             out.append(f"expression {type(e).__name__} not supported on GPU")
         for c in e.children:
             self._tag_expr(c, schema, out)
+
+    def _tag_array_search(self, e, schema, out: List[str]):
+        """array_position / array_remove compare elements (list_find):
+        fixed-width (<= 64 bit) and string elements, the rule under
+        _ARRAY_FN_NAMES. slice / array_repeat only move elements through
+        the gather, so they take what filter takes: everything but nested
+        elements, decimal128 included. dtype() checks the operand types."""
+        name = type(e).__name__
+        fn = _ARRAY_SEARCH_FNS[name]
+        if not self.conf.expr_enabled(name):
+            out.append(f"expression {name} disabled by conf")
+        rt = e.dtype(schema)
+        et = rt.children[0] if name != "ArrayPosition" \
+            else e.child.dtype(schema).children[0]
+        if et.is_nested:
+            out.append(f"{fn} over nested elements on CPU")
+        elif name in ("ArrayPosition", "ArrayRemove"):
+            if et.id is TypeId.DECIMAL128:
+                out.append(f"{fn} over decimal128 elements on CPU")
+            elif not (et.is_fixed_width or et.id is TypeId.STRING):
+                out.append(f"{fn} over {et} elements on CPU")
 
     def _tag_array_lambda(self, e, schema, out: List[str]):
         """transform / filter / exists / forall: the body runs as ordinary

@@ -735,6 +735,31 @@ class Parser:
             return -int(e.child.value)
         raise SqlError(f"expected an integer literal, got {e}")
 
+    @staticmethod
+    def _scalar_operand(e):
+        """A literal, signed or not, as its python value; anything else as
+        the expression it is."""
+        from ..expr.expressions import Literal, UnaryExpr
+
+        if isinstance(e, Literal):
+            return e.value
+        if isinstance(e, UnaryExpr) and e.op == "neg" and \
+                isinstance(e.child, Literal) and \
+                isinstance(e.child.value, (int, float)) and \
+                not isinstance(e.child.value, bool):
+            return -e.child.value
+        return e
+
+    @classmethod
+    def _int_operand(cls, e):
+        """An integer literal as a python int, else the expression."""
+        from ..expr.expressions import Literal
+
+        v = cls._scalar_operand(e)
+        if v is None:
+            return Literal(None)
+        return v
+
     def parse_func(self):
         name = self.next()[1].lower()
         self.expect_op("(")
@@ -877,6 +902,23 @@ class Parser:
                    "array_except": _ex.ArrayExcept,
                    "arrays_overlap": _ex.ArraysOverlap}[name]
             return cls(args[0], args[1])
+        if name in ("array_position", "array_remove", "array_repeat"):
+            from ..expr import expressions as _ex
+
+            if len(args) != 2:
+                raise ValueError(f"{name} takes two arguments")
+            if name == "array_repeat":
+                return _ex.ArrayRepeat(args[0], self._int_operand(args[1]))
+            cls = {"array_position": _ex.ArrayPosition,
+                   "array_remove": _ex.ArrayRemove}[name]
+            return cls(args[0], self._scalar_operand(args[1]))
+        if name == "slice":
+            from ..expr.expressions import ArraySlice
+
+            if len(args) != 3:
+                raise ValueError("slice takes three arguments")
+            return ArraySlice(args[0], self._int_operand(args[1]),
+                              self._int_operand(args[2]))
         if name in ("map_keys", "map_values", "map_entries"):
             from ..expr.expressions import MapView
 

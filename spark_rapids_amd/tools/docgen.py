@@ -225,6 +225,19 @@ _EXPR_ROWS = [
     ("ArrayForAll", "forall(a, x -> p)", "GPU*",
      "three-valued per-row reduction; the body must be GPU-supported; "
      "nested element types CPU"),
+    ("ArrayPosition", "array_position(a, v) / col.array_position(v)", "GPU",
+     "per-row search for a per-row needle (lists.hip list_find), INT64, "
+     "1-based, 0 for none; v of exactly the element type; "
+     "decimal128/nested elements CPU"),
+    ("ArrayRemove", "array_remove(a, v)", "GPU",
+     "list_find's match flags into array_distinct's compaction; null "
+     "elements kept; decimal128/nested elements CPU"),
+    ("Slice", "slice(a, start, length) / col.slice(start, length)", "GPU",
+     "offset arithmetic per row, one gather map (lists.hip); start == 0 or "
+     "length < 0 raise; nested elements CPU"),
+    ("ArrayRepeat", "array_repeat(e, n)", "GPU",
+     "lengths scan into offsets, element-to-row map as the gather map; "
+     "nested elements CPU"),
     ("CreateArray", "from_pylist lists", "CPU", "construction host-side"),
     # misc
     ("Rand", "SampleHash deterministic draw", "GPU", "sample() lowering"),
