@@ -346,6 +346,7 @@ PYBIND11_MODULE(hipdf, m) {
   BIND(mask_count);
   BIND(mask_scatter);
   BIND(gather_fixed);
+  BIND(gather_codes);
   BIND(gather_table);
   BIND(gather_validity);
   BIND(gather_str_lens);
@@ -374,6 +375,7 @@ PYBIND11_MODULE(hipdf, m) {
   BIND(gb_number);
   BIND(gb_rowgid);
   BIND(dense_gid);
+  BIND(dense_null_slot);
   BIND(gb_acc_init);
   BIND(gb_agg);
   BIND(gb_agg_multi);

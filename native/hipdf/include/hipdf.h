@@ -79,7 +79,10 @@ typedef struct {
 } HipdfGatherCol;
 HIPDF_STATIC_ASSERT(sizeof(HipdfGatherCol) == 40, "packed as <iiqqqq");
 
-/* one integer key of the dense group-id fast path (hipdf_dense_gid) */
+/* one key of the dense group-id fast path (hipdf_dense_gid). idx == NULL: an
+ * integer key column, row i reads vals[i] of `type` under `valid`. idx set:
+ * a code-table key, vals is an int32 table and row i reads vals[idx[i]];
+ * idx[i] < 0 takes the NULL slot, `type` and `valid` are not looked at. */
 typedef struct {
   int type;        /* HipdfType of the key column */
   int pad;
@@ -88,8 +91,9 @@ typedef struct {
   int64_t kmin;
   int64_t range;   /* #distinct slots for values; NULL takes index `range` */
   int64_t stride;
+  const int32_t* idx;  /* may be null; int32 rows of the table `vals` */
 } HipdfDenseKey;
-HIPDF_STATIC_ASSERT(sizeof(HipdfDenseKey) == 48, "packed as <iiqqqqq");
+HIPDF_STATIC_ASSERT(sizeof(HipdfDenseKey) == 56, "packed as <iiqqqqqq");
 
 /* one aggregate of the fused hipdf_gb_agg_multi */
 typedef struct {
@@ -190,6 +194,9 @@ void hipdf_mask_scatter(const void* mask, const void* mvalid,
 /* idx: int32[n_out] */
 void hipdf_gather_fixed(int esize, const void* in, const void* idx, void* out,
                         int64_t n_out, hipStream_t stream);
+/* in, out: int32 dictionary codes; a negative index yields the code -1 */
+void hipdf_gather_codes(const void* in, const void* idx, void* out,
+                        int64_t n_out, hipStream_t stream);
 /* cols: device HipdfGatherCol[ncols]; a negative index yields a null */
 void hipdf_gather_table(const void* cols, int ncols, const void* idx,
                         int64_t n_out, hipStream_t stream);
@@ -271,9 +278,15 @@ void hipdf_gb_number(const void* claimed_slots, const void* slot_row,
                      int64_t max_groups, hipStream_t stream);
 void hipdf_gb_rowgid(const void* row_slot, const void* slot_gid, void* row_gid,
                      int64_t n, hipStream_t stream);
-/* keys: device HipdfDenseKey[nkeys] */
+/* keys: device HipdfDenseKey[nkeys]. live: optional uint8 per dense id,
+ * zeroed by the caller; every id some row lands on is set to 1. */
 void hipdf_dense_gid(const void* keys, int nkeys, const void* sel,
-                     void* row_gid, int64_t n, hipStream_t stream);
+                     void* row_gid, void* live, int64_t n,
+                     hipStream_t stream);
+/* table: int32[n] group ids of a dictionary's rows; a row where every one of
+ * keys (device HipdfKeyCol[nkeys]) is NULL is moved to null_slot */
+void hipdf_dense_null_slot(void* table, const void* keys, int nkeys,
+                           int32_t null_slot, int64_t n, hipStream_t stream);
 /* acc init for op: 0 sum 1 min 2 max 3 count */
 void hipdf_gb_acc_init(int op, void* acc, int acc_is_double, int32_t ngroups,
                        hipStream_t stream);

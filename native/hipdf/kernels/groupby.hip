@@ -75,21 +75,48 @@ __device__ __forceinline__ int64_t dense_load_i64(const void* p, int t,
   }
 }
 
+// A key with `idx` set is a code table read through a map (a join's gather
+// map over a dimension whose rows were grouped beforehand): the fact row
+// never touches the strings, only vals[idx[i]]. `live`, when given, gets a 1
+// for every id a row lands on, which is what the compaction needs; the plain
+// read in front keeps the hot few-group case from storing to one byte from
+// every wave (a stale 0 only costs a redundant store of the same 1).
 __global__ void k_dense_gid(const DenseKey* __restrict__ keys, int nkeys,
                             const int32_t* __restrict__ sel,
-                            int32_t* __restrict__ row_gid, int64_t n) {
+                            int32_t* __restrict__ row_gid,
+                            uint8_t* __restrict__ live, int64_t n) {
   for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n;
        j += (int64_t)gridDim.x * blockDim.x) {
     int64_t i = sel ? (int64_t)sel[j] : j;
     int64_t gid = 0;
     for (int k = 0; k < nkeys; ++k) {
       const DenseKey& d = keys[k];
-      int64_t code = valid_bit(d.valid, i)
-                         ? dense_load_i64(d.vals, d.type, i) - d.kmin
-                         : d.range;
+      int64_t code;
+      if (d.idx) {
+        int32_t r = d.idx[i];
+        code = r >= 0 ? (int64_t)((const int32_t*)d.vals)[r] - d.kmin
+                      : d.range;
+      } else {
+        code = valid_bit(d.valid, i)
+                   ? dense_load_i64(d.vals, d.type, i) - d.kmin
+                   : d.range;
+      }
       gid += code * d.stride;
     }
     row_gid[j] = (int32_t)gid;
+    if (live && !live[gid]) live[gid] = 1;
+  }
+}
+
+__global__ void k_dense_null_slot(int32_t* __restrict__ table,
+                                  const KeyCol* __restrict__ keys, int nkeys,
+                                  int32_t null_slot, int64_t n) {
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n;
+       r += (int64_t)gridDim.x * blockDim.x) {
+    bool all_null = true;
+    for (int k = 0; k < nkeys; ++k)
+      all_null = all_null && keys[k].valid && !valid_bit(keys[k].valid, r);
+    if (all_null) table[r] = null_slot;
   }
 }
 
@@ -541,10 +568,18 @@ void hipdf_gb_percentile(const void* vals, const void* perm,
 }
 
 void hipdf_dense_gid(const void* keys, int nkeys, const void* sel,
-                     void* row_gid, int64_t n, hipStream_t stream) {
+                     void* row_gid, void* live, int64_t n,
+                     hipStream_t stream) {
   hipLaunchKernelGGL(k_dense_gid, flat_grid(n), dim3(HIPDF_BLOCK), 0, stream,
                      (const DenseKey*)keys, nkeys, (const int32_t*)sel,
-                     (int32_t*)row_gid, n);
+                     (int32_t*)row_gid, (uint8_t*)live, n);
+}
+
+void hipdf_dense_null_slot(void* table, const void* keys, int nkeys,
+                           int32_t null_slot, int64_t n, hipStream_t stream) {
+  hipLaunchKernelGGL(k_dense_null_slot, flat_grid(n), dim3(HIPDF_BLOCK), 0,
+                     stream, (int32_t*)table, (const KeyCol*)keys, nkeys,
+                     null_slot, n);
 }
 
 void hipdf_gb_collect_count(const void* vvalid, const void* row_gid,

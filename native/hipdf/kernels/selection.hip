@@ -90,6 +90,18 @@ __global__ void k_gather_fixed(const T* __restrict__ in,
   }
 }
 
+// dictionary codes (int32 rows of a dictionary column, -1 = NULL): a gather
+// of a dictionary view moves only these, and a missing row stays -1
+__global__ void k_gather_codes(const int32_t* __restrict__ in,
+                               const int32_t* __restrict__ idx,
+                               int32_t* __restrict__ out, int64_t n_out) {
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n_out;
+       j += (int64_t)gridDim.x * blockDim.x) {
+    int32_t i = idx[j];
+    out[j] = i >= 0 ? in[i] : -1;
+  }
+}
+
 __global__ void k_gather_validity(const uint64_t* __restrict__ in_valid,
                                   int in_has_valid,
                                   const int32_t* __restrict__ idx,
@@ -294,6 +306,13 @@ void hipdf_mask_scatter(const void* mask, const void* mvalid,
   hipLaunchKernelGGL(k_mask_scatter, dim3((uint32_t)nb), dim3(HIPDF_BLOCK), 0,
                      stream, (const uint8_t*)mask, (const uint64_t*)mvalid,
                      (const int64_t*)block_offsets, (int32_t*)out_idx, n);
+}
+
+void hipdf_gather_codes(const void* in, const void* idx, void* out,
+                        int64_t n_out, hipStream_t stream) {
+  hipLaunchKernelGGL(k_gather_codes, flat_grid(n_out), dim3(HIPDF_BLOCK), 0,
+                     stream, (const int32_t*)in, (const int32_t*)idx,
+                     (int32_t*)out, n_out);
 }
 
 void hipdf_gather_fixed(int esize, const void* in, const void* idx, void* out,

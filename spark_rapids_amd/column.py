@@ -405,6 +405,93 @@ class Column:
                 f"nulls={self.null_count})")
 
 
+class DictColumn(Column):
+    """A device STRING column held as a dictionary view: row i is
+    dictionary[codes[i]], and a code of -1 is NULL.
+
+    A hash join emits its build side's strings this way (the gather map is
+    the codes), so the strings of a few dimension rows are not copied out
+    once per fact row. `data`, `offsets` and `validity` are produced on
+    first access by the same string gather an eager join output would have
+    run, and cached; every consumer that reads them keeps working. Two
+    threads materialising at once both compute the same buffers. The
+    group-by reads `dictionary` and `codes` and never materialises."""
+
+    __slots__ = ("dictionary", "codes", "maybe_negative", "_strings",
+                 "_validity")
+
+    def __init__(self, dictionary: Column, codes: torch.Tensor, size: int,
+                 maybe_negative: bool):
+        assert dictionary.dtype.id is TypeId.STRING \
+            and not isinstance(dictionary, DictColumn)
+        assert codes.dtype == torch.int32 and codes.numel() == size
+        self.dtype = dictionary.dtype
+        self.size = size
+        self.dictionary = dictionary  # kept alive by the view
+        self.codes = codes
+        self.maybe_negative = maybe_negative
+        self.child = None
+        self._minmax = None
+        self._strings = None   # (data, offsets) once materialised
+        self._validity = None  # (mask or None,) once known
+        if size == 0 or (dictionary.validity is None and not maybe_negative):
+            # answered without a kernel (a zero-row gather has no mask)
+            self._validity = (None,)
+            self._null_count = 0
+        else:
+            self._null_count = None
+
+    @property
+    def is_materialized(self) -> bool:
+        return self._strings is not None
+
+    def _materialize(self):
+        from .ops import gpu_backend as gb
+
+        c = gb._gather_col(self.dictionary, self.codes, self.size,
+                           self.maybe_negative)
+        if self._validity is None:
+            self._validity = (c.validity,)
+        self._strings = (c.data, c.offsets)
+        return self._strings
+
+    @property
+    def data(self) -> torch.Tensor:
+        return (self._strings or self._materialize())[0]
+
+    @property
+    def offsets(self) -> torch.Tensor:
+        return (self._strings or self._materialize())[1]
+
+    @property
+    def validity(self) -> Optional[torch.Tensor]:
+        if self._validity is None:
+            from .ops import gpu_backend as gb
+
+            self._validity = (gb._gather_validity(
+                self.dictionary, self.codes, self.size),)
+        return self._validity[0]
+
+    @property
+    def device(self) -> str:
+        return "cuda"
+
+    @property
+    def is_cuda(self) -> bool:
+        return True
+
+    @property
+    def nbytes(self) -> int:
+        if self._strings is None:
+            return self.codes.numel() * 4
+        return Column.nbytes.fget(self)
+
+    def __repr__(self):
+        return (f"DictColumn({self.dtype}, size={self.size}, "
+                f"dictionary={self.dictionary.size} rows, "
+                f"materialized={self.is_materialized})")
+
+
 def _infer_dtype(np_dtype) -> DType:
     m = {
         np.dtype(np.bool_): TypeId.BOOL,

@@ -207,6 +207,13 @@ JOIN_SUBPARTITION_BYTES = int_conf(
     "Build sides larger than this are hash-split into buckets and joined "
     "bucket-by-bucket (GpuSubPartitionHashJoin analogue), bounding the "
     "peak size of any single hash table and its gather maps.")
+JOIN_DICTIONARY_STRINGS = bool_conf(
+    "spark.rapids.sql.join.dictionaryStrings.enabled", True,
+    "A GPU hash join emits its build side's STRING columns as dictionary "
+    "views (codes into the build-side column) instead of copying the "
+    "strings per output row; a group-by over such keys computes its group "
+    "ids from the codes, and any other consumer materializes the strings "
+    "on first access.")
 CPU_BRIDGE = bool_conf(
     "spark.rapids.sql.cpuBridge.enabled", True,
     "Evaluate CPU-only expressions inside GPU projections via a host "

@@ -265,15 +265,19 @@ def apply_boolean_mask(batch: ColumnBatch, mask: Column) -> ColumnBatch:
 
 
 def gather(batch: ColumnBatch, indices: Column, check_bounds: bool = False,
-           negatives: bool = True) -> ColumnBatch:
+           negatives: bool = True, dict_strings: bool = False) -> ColumnBatch:
     """Take rows by int32 index column; negative index -> null row
     (OutOfBoundsPolicy.NULLIFY analogue for join gather maps).
     negatives=False: the caller guarantees no -1 indices (inner/cross
     maps), so non-null source columns stay mask-free — otherwise a
     validity mask re-materializes on every gathered column and defeats
-    the downstream non-null fast paths."""
-    return backend_for(*batch.columns, indices).gather(
-        batch, indices, check_bounds, negatives)
+    the downstream non-null fast paths.
+    dict_strings=True (a hash join's build side, GPU backend only): STRING
+    columns come back as dictionary views over `indices` (DictColumn)."""
+    backend = backend_for(*batch.columns, indices)
+    if dict_strings and backend is not cpu_backend:
+        return backend.gather_dict(batch, indices, negatives)
+    return backend.gather(batch, indices, check_bounds, negatives)
 
 
 def murmur3_hash(cols: Sequence[Column], seed: int = 42) -> Column:

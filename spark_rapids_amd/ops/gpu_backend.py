@@ -15,7 +15,8 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
-from ..column import Column, ColumnBatch, mask_nbytes, torch_dtype
+from ..column import (Column, ColumnBatch, DictColumn, mask_nbytes,
+                      torch_dtype)
 from ..types import DType, TypeId
 from .cpu_backend import SLICE_LENGTH_ERROR, SLICE_START_ERROR
 
@@ -1925,11 +1926,51 @@ def gather(batch: ColumnBatch, indices: Column, check_bounds: bool = False,
                           maybe_negative=negatives)
 
 
+def gather_dict(batch: ColumnBatch, indices: Column,
+                negatives: bool = True) -> ColumnBatch:
+    """gather() for a join's build side: STRING columns come back as
+    dictionary views over the gather map instead of copied strings."""
+    n_out = indices.size
+    idx = indices.data
+    if idx.numel() != n_out:
+        idx = idx[:n_out]  # one tensor object: the views share their codes
+    return _gather_by_idx(batch, idx, n_out, maybe_negative=negatives,
+                          dict_strings=True)
+
+
+def _gather_validity(c: Column, idx: torch.Tensor,
+                     n_out: int) -> torch.Tensor:
+    ov = _alloc_mask(n_out)
+    ext.gather_validity(_ptr(c.validity), c.validity is not None,
+                        idx.data_ptr(), ov.data_ptr(), n_out, _stream())
+    return ov
+
+
+def _gather_view(c: DictColumn, idx: torch.Tensor, n_out: int,
+                 maybe_negative: bool, shared: Optional[dict] = None
+                 ) -> DictColumn:
+    """Gather of a dictionary view: only the codes move, the result is a
+    view over the same dictionary. `shared` maps id(codes) to the gathered
+    codes, so views that shared their codes going in still do coming out
+    (the group-by groups such keys jointly)."""
+    codes = shared.get(id(c.codes)) if shared is not None else None
+    if codes is None:
+        codes = torch.empty(n_out, dtype=torch.int32, device="cuda")
+        ext.gather_codes(c.codes.data_ptr(), idx.data_ptr(),
+                         codes.data_ptr(), n_out, _stream())
+        if shared is not None:
+            shared[id(c.codes)] = codes
+    return DictColumn(c.dictionary, codes, n_out,
+                      c.maybe_negative or maybe_negative)
+
+
 def _gather_col(c: Column, idx: torch.Tensor, n_out: int,
                 maybe_negative: bool) -> Column:
     s = _stream()
     if n_out == 0:
         return _empty_col(c.dtype)
+    if isinstance(c, DictColumn):
+        return _gather_view(c, idx, n_out, maybe_negative)
     if c.dtype.id is TypeId.STRUCT:
         kids = tuple(_gather_col(k, idx, n_out, maybe_negative)
                      for k in c.child)
@@ -1975,12 +2016,19 @@ def _gather_col(c: Column, idx: torch.Tensor, n_out: int,
 
 
 def _gather_by_idx(batch: ColumnBatch, idx: torch.Tensor, n_out: int,
-                   maybe_negative: bool) -> ColumnBatch:
+                   maybe_negative: bool,
+                   dict_strings: bool = False) -> ColumnBatch:
     s = _stream()
     cols: List[Optional[Column]] = [None] * len(batch.columns)
     fixed: List[tuple] = []  # (position, column)
+    shared: dict = {}  # gathered codes of the views, by id(source codes)
     for ci, c in enumerate(batch.columns):
-        if c.dtype.id in (TypeId.STRING, TypeId.STRUCT) or n_out == 0:
+        if isinstance(c, DictColumn) and n_out:
+            # composes when `batch` is itself a join's build side
+            cols[ci] = _gather_view(c, idx, n_out, maybe_negative, shared)
+        elif dict_strings and c.dtype.id is TypeId.STRING and n_out:
+            cols[ci] = DictColumn(c, idx, n_out, maybe_negative)
+        elif c.dtype.id in (TypeId.STRING, TypeId.STRUCT) or n_out == 0:
             cols[ci] = _gather_col(c, idx, n_out, maybe_negative)
         else:
             fixed.append((ci, c))
@@ -2011,8 +2059,20 @@ def concat_batches(batches: List[ColumnBatch]) -> ColumnBatch:
     total = sum(b.num_rows for b in batches)
     ncols = batches[0].num_columns
     out_cols = []
+    cat_codes: dict = {}  # concatenated codes by the ids of their inputs
     for ci in range(ncols):
         ins = [b.columns[ci] for b in batches]
+        if total and all(isinstance(c, DictColumn)
+                         and c.dictionary is ins[0].dictionary for c in ins):
+            # views over one dictionary: concatenate the codes, and keep
+            # columns that shared their codes sharing them
+            key = tuple(id(c.codes) for c in ins)
+            if key not in cat_codes:
+                cat_codes[key] = torch.cat([c.codes for c in ins])
+            out_cols.append(DictColumn(
+                ins[0].dictionary, cat_codes[key], total,
+                any(c.maybe_negative for c in ins)))
+            continue
         if ins[0].dtype.id is TypeId.LIST:
             raise NotImplementedError(
                 "concat of LIST columns on GPU (explode or collect before "
@@ -2244,31 +2304,19 @@ def group_by_aggregate(batch: ColumnBatch, key_idx: List[int],
         ngroups = 1
         leaders = torch.zeros(1, dtype=torch.int32, device="cuda")
     elif (dense := _try_dense_keys(keys, aggs, selp, n)) is not None:
-        # dense integer-key fast path: gid = radix index over the small
-        # value ranges — no hash table, no probe, no leader gather
-        # (k_dense_gid); empty ids are compacted after aggregation
+        # dense fast path: gid = radix index over small integer ranges and
+        # over the group tables of dictionary-view keys — no hash table, no
+        # probe and no string at this row count (k_dense_gid); empty ids
+        # are compacted after aggregation
         row_gid, ngroups, dense_info = dense
         leaders = None
     else:
-        h = _murmur3_tensor(keys, 42, sel, n)
-        cap = max(1024, _next_pow2(2 * n))
-        desc = _key_desc(keys)
-        slot_row = torch.full((cap,), -1, dtype=torch.int32, device="cuda")
-        row_slot = torch.empty(n, dtype=torch.int32, device="cuda")
-        claimed = torch.empty(n, dtype=torch.int32, device="cuda")
-        ngroups_t = torch.zeros(1, dtype=torch.int32, device="cuda")
-        ext.gb_build(h.data_ptr(), desc.data_ptr(), len(keys), selp,
-                     slot_row.data_ptr(), row_slot.data_ptr(),
-                     claimed.data_ptr(), ngroups_t.data_ptr(), cap, n, s)
-        slot_gid = torch.empty(cap, dtype=torch.int32, device="cuda")
-        leaders = torch.empty(n, dtype=torch.int32, device="cuda")
-        ext.gb_number(claimed.data_ptr(), slot_row.data_ptr(),
-                      slot_gid.data_ptr(), ngroups_t.data_ptr(),
-                      leaders.data_ptr(), n, s)
-        ngroups = int(ngroups_t.item())
-        row_gid = torch.empty(n, dtype=torch.int32, device="cuda")
-        ext.gb_rowgid(row_slot.data_ptr(), slot_gid.data_ptr(),
-                      row_gid.data_ptr(), n, s)
+        # today's path over materialised strings; the result's key columns
+        # are ordinary columns, not views of the views
+        keys = [Column(k.dtype, k.size, k.data, k.validity, k.offsets,
+                       k._null_count) if isinstance(k, DictColumn) else k
+                for k in keys]
+        row_gid, ngroups, leaders = _hash_group_ids(keys, sel, n)
     if leaders is not None:
         leaders = leaders[:ngroups]
     # leaders are ORIGINAL row ids (pre-selection), so gather keys from the
@@ -2425,17 +2473,83 @@ _DENSE_OK = {TypeId.BOOL, TypeId.INT8, TypeId.INT16, TypeId.INT32,
              TypeId.INT64, TypeId.DATE32}
 
 
+def _hash_group_ids(keys, sel, n):
+    """Hash path: (row_gid[n], ngroups, leaders) with one leader row (an
+    ORIGINAL row id, pre-selection) per group."""
+    s = _stream()
+    selp = 0 if sel is None else sel.data_ptr()
+    h = _murmur3_tensor(keys, 42, sel, n)
+    cap = max(1024, _next_pow2(2 * n))
+    desc = _key_desc(keys)
+    slot_row = torch.full((cap,), -1, dtype=torch.int32, device="cuda")
+    row_slot = torch.empty(n, dtype=torch.int32, device="cuda")
+    claimed = torch.empty(n, dtype=torch.int32, device="cuda")
+    ngroups_t = torch.zeros(1, dtype=torch.int32, device="cuda")
+    ext.gb_build(h.data_ptr(), desc.data_ptr(), len(keys), selp,
+                 slot_row.data_ptr(), row_slot.data_ptr(),
+                 claimed.data_ptr(), ngroups_t.data_ptr(), cap, n, s)
+    slot_gid = torch.empty(cap, dtype=torch.int32, device="cuda")
+    leaders = torch.empty(n, dtype=torch.int32, device="cuda")
+    ext.gb_number(claimed.data_ptr(), slot_row.data_ptr(),
+                  slot_gid.data_ptr(), ngroups_t.data_ptr(),
+                  leaders.data_ptr(), n, s)
+    ngroups = int(ngroups_t.item())
+    row_gid = torch.empty(n, dtype=torch.int32, device="cuda")
+    ext.gb_rowgid(row_slot.data_ptr(), slot_gid.data_ptr(),
+                  row_gid.data_ptr(), n, s)
+    return row_gid, ngroups, leaders
+
+
+def _dict_group_table(dicts: List[Column], need_null_slot: bool):
+    """Group the rows of the dictionary columns `dicts` (one dimension's
+    columns, grouped jointly) with the hash path, at dimension scale.
+    Returns (table, G, leaders, has_null_slot): table[r] is the group of
+    dictionary row r in [0, G), leaders[g] one dictionary row of group g.
+    With a NULL slot, slot G stands for "every key NULL": rows coded -1 go
+    there, and so do dictionary rows whose strings are all NULL, so that
+    both kinds of NULL key make one group (leaders[G] = -1)."""
+    d = dicts[0].size
+    if d == 0:
+        table = torch.zeros(0, dtype=torch.int32, device="cuda")
+        leaders = torch.full((1,), -1, dtype=torch.int32, device="cuda")
+        return table, 0, leaders, True
+    table, g, leaders = _hash_group_ids(dicts, None, d)
+    all_null_rows = all(c.validity is not None for c in dicts)
+    if all_null_rows:
+        ext.dense_null_slot(table.data_ptr(), _key_desc(dicts).data_ptr(),
+                            len(dicts), g, d, _stream())
+    has_null_slot = need_null_slot or all_null_rows
+    leaders = leaders[:g]
+    if has_null_slot:
+        leaders = torch.cat([leaders, torch.full(
+            (1,), -1, dtype=torch.int32, device="cuda")])
+    return table, g, leaders, has_null_slot
+
+
 def _try_dense_keys(keys, aggs, selp, n):
-    """Dense path applicability: all keys are non-null small-range integers
-    and the range product stays tiny relative to n."""
-    if any(k.validity is not None for k in keys):
+    """Dense path applicability: every key is a non-null small-range
+    integer or a dictionary view, and the product of the ranges stays tiny
+    relative to n. Views that share their codes (columns of one dimension)
+    form one radix component, grouped jointly at dimension scale."""
+    ints = [k for k in keys if not isinstance(k, DictColumn)]
+    if any(k.dtype.id not in _DENSE_OK for k in ints):
         return None
-    if any(k.dtype.id not in _DENSE_OK for k in keys):
+    if any(k.validity is not None for k in ints):
         return None
     if any(op in ("collect_list", "collect_set") for op, _, _ in aggs):
         return None  # LIST columns cannot be re-gathered in compaction
-    mins, ranges = [], []
-    for k in keys:
+    # components in key order: ("int", [pos], kmin, range) or
+    # ("dict", [pos...], codes) for the views sharing one codes tensor
+    comps: List[list] = []
+    by_codes: dict = {}
+    for i, k in enumerate(keys):
+        if isinstance(k, DictColumn):
+            comp = by_codes.get(id(k.codes))
+            if comp is None:
+                comp = by_codes[id(k.codes)] = ["dict", [], k.codes]
+                comps.append(comp)
+            comp[1].append(i)
+            continue
         if k._minmax is None:
             # cached on the column: stored tables are re-scanned every
             # query, and columns are immutable by convention
@@ -2446,66 +2560,104 @@ def _try_dense_keys(keys, aggs, selp, n):
         rng = int(kmax) - int(kmin) + 1
         if rng <= 0:
             return None
-        mins.append(int(kmin))
-        ranges.append(rng)
+        comps.append(["int", [i], int(kmin), rng])
+    limit = min(1 << 24, max(1 << 16, 4 * n))
     prod = 1
-    for r in ranges:
-        prod *= r
-        if prod > (1 << 24):
+    for comp in comps:
+        if comp[0] == "int":
+            prod *= comp[3]
+            if prod > limit:
+                return None
+    sizes = []
+    for comp in comps:
+        if comp[0] == "int":
+            sizes.append(comp[3])
+            continue
+        views = [keys[i] for i in comp[1]]
+        table, g, leaders, has_null = _dict_group_table(
+            [v.dictionary for v in views],
+            any(v.maybe_negative for v in views))
+        comp.extend([table, g, leaders, has_null])
+        sizes.append(g + (1 if has_null else 0))
+        prod *= sizes[-1]
+        if prod > limit:
             return None
-    if prod > max(1 << 16, 4 * n):
-        return None
-    strides = [0] * len(keys)
+    strides = [0] * len(comps)
     acc = 1
-    for i in range(len(keys) - 1, -1, -1):
+    for i in range(len(comps) - 1, -1, -1):
         strides[i] = acc
-        acc *= ranges[i]
+        acc *= sizes[i]
     s = _stream()
     # HipdfDenseKey (see native/hipdf/include/hipdf.h)
-    blob = b"".join(
-        struct.pack("<iiqqqqq", _ht(k.dtype), 0, k.data.data_ptr(), 0,
-                    mins[i], ranges[i], strides[i])
-        for i, k in enumerate(keys))
-    desc = torch.frombuffer(bytearray(blob), dtype=torch.uint8).cuda()
+    blobs = []
+    for comp, stride in zip(comps, strides):
+        if comp[0] == "int":
+            k = keys[comp[1][0]]
+            blobs.append(struct.pack("<iiqqqqqq", _ht(k.dtype), 0,
+                                     k.data.data_ptr(), 0, comp[2], comp[3],
+                                     stride, 0))
+        else:
+            blobs.append(struct.pack("<iiqqqqqq", 3, 0, comp[3].data_ptr(),
+                                     0, 0, comp[4], stride,
+                                     comp[2].data_ptr()))
+    desc = torch.frombuffer(bytearray(b"".join(blobs)),
+                            dtype=torch.uint8).cuda()
     row_gid = torch.empty(n, dtype=torch.int32, device="cuda")
-    ext.dense_gid(desc.data_ptr(), len(keys), selp, row_gid.data_ptr(), n, s)
-    return row_gid, prod, (mins, ranges, strides)
+    # without a count_all aggregate the compaction learns the live ids from
+    # flags set in this same pass instead of counting every row again
+    live = None
+    if not any(op == "count_all" for op, _, _ in aggs):
+        live = torch.zeros(max(prod, 1), dtype=torch.uint8, device="cuda")
+    ext.dense_gid(desc.data_ptr(), len(comps), selp, row_gid.data_ptr(),
+                  _ptr(live), n, s)
+    return row_gid, prod, (comps, sizes, strides, live)
 
 
 def _compact_dense(out_cols, allocs, keys, dense_info, ngroups, row_gid,
                    n, s):
     """Drop empty dense group ids and reconstruct the key columns from the
-    surviving ids (kmin + (g // stride) % range per key)."""
-    mins, ranges, strides = dense_info
-    counts = None
-    for (op, _, _, acc, cnt, _sk) in allocs:
-        if op == "count_all":
-            counts = cnt
-            break
-    if counts is None:
-        counts = torch.zeros(max(ngroups, 1), dtype=torch.int64,
-                             device="cuda")
-        if n:
-            ext.gb_collect_count(0, row_gid.data_ptr(), 0,
-                                 counts.data_ptr(), n, s)
-    ccol = Column(DType.int64(), ngroups, counts[:ngroups], None,
-                  null_count=0)
-    live = binary_op_scalar("gt", ccol, 0, DType.bool_())
+    surviving ids: an integer key is kmin + (g // stride) % range, a
+    dictionary key a gather of its dictionary by the leader row of group
+    (g // stride) % size, at result scale."""
+    comps, sizes, strides, live_flags = dense_info
+    if live_flags is not None:
+        live = Column(DType.bool_(), ngroups, live_flags[:ngroups], None,
+                      null_count=0)
+    else:
+        counts = next(cnt for (op, _, _, _acc, cnt, _sk) in allocs
+                      if op == "count_all")
+        ccol = Column(DType.int64(), ngroups, counts[:ngroups], None,
+                      null_count=0)
+        live = binary_op_scalar("gt", ccol, 0, DType.bool_())
     gsel = mask_to_sel(live, ngroups)
     ncomp = gsel.numel()
     gcol = Column(DType.int32(), ncomp, gsel, None, null_count=0)
     g64 = cast(gcol, DType.int64())
-    key_cols = []
-    for i, k in enumerate(keys):
+    key_cols: List[Optional[Column]] = [None] * len(keys)
+    for i, comp in enumerate(comps):
         code = g64
         if strides[i] != 1:
             code = binary_op_scalar("int_div", code, strides[i],
                                     DType.int64())
         if i > 0:  # leading key needs no modulo (gid < stride_{i-1}*range)
-            code = binary_op_scalar("mod", code, ranges[i], DType.int64())
-        if mins[i]:
-            code = binary_op_scalar("add", code, mins[i], DType.int64())
-        key_cols.append(cast(code, k.dtype))
+            code = binary_op_scalar("mod", code, sizes[i], DType.int64())
+        if comp[0] == "int":
+            if comp[2]:
+                code = binary_op_scalar("add", code, comp[2], DType.int64())
+            key_cols[comp[1][0]] = cast(code, keys[comp[1][0]].dtype)
+            continue
+        leaders, has_null = comp[5], comp[6]
+        if ncomp == 0:
+            for pos in comp[1]:
+                key_cols[pos] = _empty_col(keys[pos].dtype)
+            continue
+        slot = cast(code, DType.int32())
+        rows = torch.empty(ncomp, dtype=torch.int32, device="cuda")
+        ext.gather_codes(leaders.data_ptr(), slot.data.data_ptr(),
+                         rows.data_ptr(), ncomp, s)
+        for pos in comp[1]:
+            key_cols[pos] = _gather_col(keys[pos].dictionary, rows, ncomp,
+                                        maybe_negative=has_null)
     agg_batch = _gather_by_idx(ColumnBatch(out_cols, ngroups), gsel, ncomp,
                                maybe_negative=False)
     return ColumnBatch(key_cols + list(agg_batch.columns), ncomp)

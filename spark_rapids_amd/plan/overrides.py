@@ -562,7 +562,8 @@ def _convert(node: L.LogicalPlan, conf: RapidsConf, tagger: Tagger,
             right_replicated=L.is_replicated(node.right),
             condition=node.condition)
     if isinstance(node, L.Join):
-        from ..config import BROADCAST_THRESHOLD, JOIN_SUBPARTITION_BYTES
+        from ..config import (BROADCAST_THRESHOLD, JOIN_DICTIONARY_STRINGS,
+                              JOIN_SUBPARTITION_BYTES)
 
         return P.HashJoinExec(device, kids[0], kids[1], node.left_on,
                               node.right_on, node.how, node.schema(),
@@ -570,7 +571,8 @@ def _convert(node: L.LogicalPlan, conf: RapidsConf, tagger: Tagger,
                               broadcast_threshold=conf.get(BROADCAST_THRESHOLD),
                               sub_partition_bytes=conf.get(
                                   JOIN_SUBPARTITION_BYTES),
-                              using=node.using, condition=node.condition)
+                              using=node.using, condition=node.condition,
+                              dict_strings=conf.get(JOIN_DICTIONARY_STRINGS))
     if isinstance(node, L.MapBatches):
         return P.MapBatchesExec(node.fn, _ensure_device(kids[0], "cpu"),
                                 node.schema())

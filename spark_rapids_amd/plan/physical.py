@@ -544,8 +544,13 @@ class HashJoinExec(PhysicalExec):
                  schema: Schema, right_replicated: bool = True,
                  broadcast_threshold: int = 512 << 20,
                  sub_partition_bytes: int = 1 << 30,
-                 using: bool = False, condition=None):
+                 using: bool = False, condition=None,
+                 dict_strings: bool = False):
         super().__init__(device, schema, [left, right])
+        # emit the build side's STRING columns as dictionary views over the
+        # gather map (GPU only; the conditional and sub-partitioned paths
+        # gather eagerly)
+        self.dict_strings = dict_strings and self.gpu
         self.left_on = left_on
         self.right_on = right_on
         self.how = how
@@ -663,7 +668,8 @@ class HashJoinExec(PhysicalExec):
                 continue
             lout = ops.gather(lbatch, lmap, negatives=False)
             rout = ops.gather(rtable, rmap,
-                              negatives=self.how in ("left", "full"))
+                              negatives=self.how in ("left", "full"),
+                              dict_strings=self.dict_strings)
             if lout.num_rows:
                 yield ColumnBatch(lout.columns +
                                   self._right_out(rout), lout.num_rows)
