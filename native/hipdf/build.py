@@ -40,6 +40,7 @@ KERNELS = [
     "kernels/datetime.hip",
     "kernels/lists.hip",
     "pool.hip",
+    "scan_reader.hip",
 ]
 
 CXXFLAGS = ["-O3", "-std=c++20", "-fPIC", f"--offload-arch={ARCH}",

@@ -329,6 +329,46 @@ PYBIND11_MODULE(hipdf, m) {
         },
         py::call_guard<py::gil_scoped_release>());
 
+  // ---- native in-order scan reader ---------------------------------------
+  // handles and tickets are plain integers; every call that can block
+  // (thread start, page walk, waiting for a group, draining) releases the GIL
+  m.def("pq_plain_pieces",
+        [](int64_t chunk, int64_t nbytes, int64_t num_values, int max_def,
+           int phys_width, int64_t out, int64_t max_out) -> int64_t {
+          return hipdf_pq_plain_pieces((const void*)chunk, nbytes, num_values,
+                                       max_def, phys_width, (int64_t*)out,
+                                       max_out);
+        },
+        py::call_guard<py::gil_scoped_release>());
+  m.def("scan_open",
+        [](int n_threads, int n_streams, int64_t piece_bytes) -> int64_t {
+          return (int64_t)hipdf_scan_open(n_threads, n_streams, piece_bytes);
+        },
+        py::call_guard<py::gil_scoped_release>());
+  m.def("scan_submit",
+        [](int64_t reader, int64_t chunks, int64_t n_chunks, int n_groups,
+           int64_t consumer) -> int64_t {
+          return hipdf_scan_submit((HipdfScanReader*)reader,
+                                   (const HipdfScanChunk*)chunks, n_chunks,
+                                   n_groups, to_c<hipStream_t>(consumer));
+        },
+        py::call_guard<py::gil_scoped_release>());
+  m.def("scan_wait_group",
+        [](int64_t reader, int64_t ticket, int group,
+           int64_t consumer) -> int {
+          return hipdf_scan_wait_group((HipdfScanReader*)reader, ticket,
+                                       group, to_c<hipStream_t>(consumer));
+        },
+        py::call_guard<py::gil_scoped_release>());
+  m.def("scan_cancel",
+        [](int64_t reader, int64_t ticket) {
+          hipdf_scan_cancel((HipdfScanReader*)reader, ticket);
+        },
+        py::call_guard<py::gil_scoped_release>());
+  m.def("scan_close",
+        [](int64_t reader) { hipdf_scan_close((HipdfScanReader*)reader); },
+        py::call_guard<py::gil_scoped_release>());
+
   // ---- elementwise -------------------------------------------------------
   BIND(binary_arith);
   BIND(binary_cmp);

@@ -767,6 +767,56 @@ void hipdf_list_slice_map(const void* new_offs, const void* src_start,
                           int64_t n, void* idx, int64_t total,
                           hipStream_t stream);
 
+/* ---- native in-order scan reader (scan_reader.hip) --------------------- */
+/* Host-only walk of one parquet column chunk: one (value offset from the
+ * chunk start, value bytes, values) int64 triple per data page into out
+ * (room for max_out triples). Returns the number of pages, or a negative
+ * code when the chunk is not eligible: eligible is uncompressed, no
+ * dictionary page, every data page (v1 or v2) PLAIN with phys_width 4 or 8
+ * bytes per value, and max_def == 0 or every page's definition levels plain
+ * RLE runs of max_def. Never reads at or beyond chunk + nbytes. */
+int64_t hipdf_pq_plain_pieces(const void* chunk, int64_t nbytes,
+                              int64_t num_values, int max_def, int phys_width,
+                              int64_t* out, int64_t max_out);
+
+/* one column chunk of a scan submit; the array stays in host memory */
+typedef struct {
+  const void* src;     /* host: first byte of the chunk in the file mapping */
+  int64_t nbytes;      /* chunk length */
+  int32_t phys_width;  /* 4 or 8 */
+  int32_t dst_width;   /* phys_width, or 8 over 4: signed widen */
+  void* dst;           /* device: where the chunk's first value lands */
+  int64_t num_values;
+  int32_t group;       /* hand-over unit (file index), 0 .. n_groups-1 */
+  int32_t max_def;
+} HipdfScanChunk;
+HIPDF_STATIC_ASSERT(sizeof(HipdfScanChunk) == 48, "packed as <qqiiqqii");
+
+typedef struct HipdfScanReader HipdfScanReader;
+/* at most 8 worker threads, each with a scratch buffer of piece_bytes;
+ * n_streams <= n_threads copy streams. NULL on failure. */
+HipdfScanReader* hipdf_scan_open(int n_threads, int n_streams,
+                                 int64_t piece_bytes);
+/* Walks every chunk, cuts it into pieces of at most piece_bytes and queues
+ * them group-major. Every dst buffer must be allocated before the call (see
+ * the memory rule in scan_reader.hip); an event recorded on `consumer` gates
+ * the first write. Returns a ticket (> 0), or a negative code and nothing
+ * queued: a hipdf_pq_plain_pieces code when a chunk is not eligible. */
+int64_t hipdf_scan_submit(HipdfScanReader* r, const HipdfScanChunk* chunks,
+                          int64_t n_chunks, int n_groups,
+                          hipStream_t consumer);
+/* Blocks the calling thread until every piece of `group` is enqueued, then
+ * makes `consumer` wait for them on the device. 0, or negative on a copy
+ * error / a cancelled submit. */
+int hipdf_scan_wait_group(HipdfScanReader* r, int64_t ticket, int group,
+                          hipStream_t consumer);
+/* Ends a submit, finished or not: claims no further piece, waits for what
+ * is claimed to be enqueued and, when a group with copies was never waited
+ * for, for the copies themselves. Every ticket must be cancelled once. */
+void hipdf_scan_cancel(HipdfScanReader* r, int64_t ticket);
+/* cancels what is left, joins the workers, frees streams and scratch */
+void hipdf_scan_close(HipdfScanReader* r);
+
 /* ---- device memory pool (pool.hip) ------------------------------------- */
 /* reserve `bytes` (or fraction of free memory if bytes==0) as the pool
  * slab; returns 0 on success */

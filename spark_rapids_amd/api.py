@@ -255,9 +255,17 @@ class DataFrame:
         instrument(exec_)
         self._last_exec = exec_
         sem = GpuSemaphore.get()
+        from .plan.physical import start_stream_scans, stop_stream_scans
+
         try:
             with sem.held():
-                batches = [b.cpu() for b in exec_.execute()]
+                # the fact upload starts now and runs under the dimension
+                # scans and join builds that execute before its first pull
+                started = start_stream_scans(exec_)
+                try:
+                    batches = [b.cpu() for b in exec_.execute()]
+                finally:
+                    stop_stream_scans(started)
         except (RuntimeError, MemoryError) as e:
             from .tools import crashdump
 
@@ -574,12 +582,16 @@ class Session:
         if reader == "AUTO":
             reader = "GPU_DECODE" if (torch.cuda.is_available()
                                       and self.conf.sql_enabled) else "CPU"
-        from .config import BATCH_SIZE_BYTES
+        from .config import (BATCH_SIZE_BYTES, PARQUET_STREAM_SCAN,
+                             PARQUET_STREAM_SCAN_FILES)
 
         src = ParquetTable(path, columns=columns, reader=reader,
                            prefetch_threads=self.conf.get(PARQUET_MT_THREADS),
                            replicated=replicated,
-                           chunk_bytes=self.conf.get(BATCH_SIZE_BYTES))
+                           chunk_bytes=self.conf.get(BATCH_SIZE_BYTES),
+                           stream_scan=self.conf.get(PARQUET_STREAM_SCAN),
+                           stream_files=self.conf.get(
+                               PARQUET_STREAM_SCAN_FILES))
         return DataFrame(self, L.Scan(src, src.schema, f"parquet:{path}"))
 
     def write_parquet(self, df: DataFrame, path: str,

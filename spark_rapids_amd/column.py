@@ -100,7 +100,7 @@ class Column:
     """One column of data; immutable by convention."""
 
     __slots__ = ("dtype", "size", "data", "validity", "offsets",
-                 "_null_count", "child", "_minmax")
+                 "_null_count", "child", "_minmax", "_group_tables")
 
     def __init__(
         self,
@@ -119,7 +119,12 @@ class Column:
         self.offsets = offsets
         self._null_count = null_count
         self.child = child  # LIST element column / tuple for STRUCT
-        self._minmax = None  # cached (min, max) for dense-key group-by
+        # cached (min, max) for dense-key group-by, or the join build column
+        # whose range this column inherits (gpu_backend._key_minmax)
+        self._minmax = None
+        # group tables of the dictionary sets this column leads
+        # (gpu_backend._dict_group_table)
+        self._group_tables = None
         if dtype.id is TypeId.STRING:
             assert offsets is not None and offsets.numel() == size + 1
         if dtype.id in (TypeId.LIST, TypeId.MAP):
@@ -432,6 +437,7 @@ class DictColumn(Column):
         self.maybe_negative = maybe_negative
         self.child = None
         self._minmax = None
+        self._group_tables = None
         self._strings = None   # (data, offsets) once materialised
         self._validity = None  # (mask or None,) once known
         if size == 0 or (dictionary.validity is None and not maybe_negative):

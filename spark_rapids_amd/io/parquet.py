@@ -147,7 +147,10 @@ def parquet_schema(path: str) -> Schema:
 # observability for GPU-vs-fallback scan routing (the bench and GPU tests
 # assert the device decode path actually ran — VERDICT: no silent fallback)
 SCAN_STATS = {"gpu_files": 0, "fallback_files": 0, "last_fallback": None,
-              "rg_skipped": 0, "rg_scanned": 0}
+              "rg_skipped": 0, "rg_scanned": 0,
+              # multi-file GPU_DECODE scans with streamScan enabled: taken by
+              # the native in-order reader / run by the per-file path instead
+              "stream_scans": 0, "stream_scans_not_eligible": 0}
 # cumulative host-side phase timers for the GPU decode path (seconds,
 # summed across prefetch threads — can exceed wall when overlapped)
 PHASE_STATS = {"meta_s": 0.0, "io_s": 0.0, "decode_s": 0.0,
@@ -220,7 +223,15 @@ class ParquetTable:
     def __init__(self, path: str, num_partitions: int = 0,
                  columns: Optional[List[str]] = None, reader: str = "CPU",
                  prefetch_threads: int = 4, replicated: bool = False,
-                 chunk_bytes: int = 0):
+                 chunk_bytes: int = 0, stream_scan: bool = False,
+                 stream_files: int = 4, stream_piece_bytes: int = 0):
+        # stream_scan: multi-file GPU_DECODE scans of PLAIN fixed-width
+        # chunks go through the native in-order reader, one batch per
+        # stream_files files (parquet_gpu.StreamScan); stream_piece_bytes
+        # overrides the reader's piece size (0 = its default)
+        self.stream_scan = stream_scan
+        self.stream_files = stream_files
+        self.stream_piece_bytes = stream_piece_bytes
         # chunk_bytes > 0: a file whose decoded size exceeds the budget is
         # read ROW GROUP by row group as separate batches instead of one
         # concatenated file batch (the chunked-reader analogue:
@@ -259,6 +270,9 @@ class ParquetTable:
         t.schema = self.schema
         t.rg_predicate = getattr(self, "rg_predicate", None)
         t.chunk_bytes = getattr(self, "chunk_bytes", 0)
+        t.stream_scan = getattr(self, "stream_scan", False)
+        t.stream_files = getattr(self, "stream_files", 4)
+        t.stream_piece_bytes = getattr(self, "stream_piece_bytes", 0)
         return t
 
     def with_columns(self, names: List[str]) -> "ParquetTable":
@@ -371,7 +385,45 @@ class ParquetTable:
             return self.files[c.rank::c.world]
         return self.files
 
+    def start_stream_scan(self):
+        """Submit this scan to the native in-order reader and return the
+        running parquet_gpu.StreamScan, or None when the scan is not one
+        for it (single file, another reader, conf off, host file cache on,
+        or a chunk that is not PLAIN fixed-width without nulls). The caller
+        consumes batches() or calls close()."""
+        import torch
+
+        if not getattr(self, "stream_scan", False) \
+                or self.reader != "GPU_DECODE" \
+                or not torch.cuda.is_available():
+            return None
+        files = self._my_files()
+        if len(files) <= 1:
+            return None
+        from . import filecache
+
+        if filecache._enabled:
+            return None
+        from .parquet_gpu import StreamScan
+
+        scan = StreamScan.start(self, files)
+        if scan is None:
+            SCAN_STATS["stream_scans_not_eligible"] += 1
+            return None
+        SCAN_STATS["stream_scans"] += 1
+        SCAN_STATS["gpu_files"] += len(files)
+        return scan
+
     def partitions(self) -> Iterable[ColumnBatch]:
+        scan = self.start_stream_scan()
+        if scan is not None:
+            yield from scan.batches()
+            return
+        yield from self.partitions_per_file()
+
+    def partitions_per_file(self) -> Iterable[ColumnBatch]:
+        """The scan without the native in-order reader: one read per file on
+        the prefetch pool."""
         files = self._my_files()
         if len(files) <= 1 or self.prefetch_threads <= 1:
             for f in files:

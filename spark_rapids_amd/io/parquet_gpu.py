@@ -966,6 +966,230 @@ def read_parquet_gpu(path: str, columns: List[str],
             rg_batches.append(ColumnBatch(cols, rgmd.num_rows))
     if len(rg_batches) == 1:
         return rg_batches[0]
+    if not rg_batches:
+        # a file without row groups (written from an empty table)
+        return ColumnBatch(
+            [Column.nulls(arrow_to_dtype(arrow_schema.field(n).type), 0,
+                          "cuda") for n in columns], 0)
     from ..ops import gpu_backend as gb
 
     return gb.concat_batches(rg_batches)
+
+
+# ---------------------------------------------------------------------------
+# stream scan: several files of PLAIN fixed-width chunks through the native
+# in-order reader (native/hipdf/scan_reader.hip)
+# ---------------------------------------------------------------------------
+
+STREAM_PIECE_BYTES = 4 << 20  # one 1M-row page of a 4-byte column
+# copy streams the reader's workers share: one was slower, two, three and
+# eight measured the same (profiles/r14_scan_stream.md)
+STREAM_COPY_STREAMS = 2
+
+_PHYS_WIDTH = {"INT32": 4, "INT64": 8, "FLOAT": 4, "DOUBLE": 8}
+# (files, columns, predicate) -> (mtimes, layout or None)
+_STREAM_LAYOUTS: dict = {}
+# (threads, streams, piece_bytes) -> native reader handle, closed at exit
+_READERS: dict = {}
+_READERS_LOCK = __import__("threading").Lock()
+
+
+def _close_readers():
+    from ..ops.gpu_backend import ext
+
+    with _READERS_LOCK:
+        handles = list(_READERS.values())
+        _READERS.clear()
+    for h in handles:
+        ext.scan_close(h)
+
+
+def _reader(threads: int, piece_bytes: int) -> int:
+    from ..ops.gpu_backend import ext
+
+    threads = max(1, min(int(threads), 8))
+    streams = max(1, min(int(STREAM_COPY_STREAMS), threads))
+    key = (threads, streams, int(piece_bytes))
+    with _READERS_LOCK:
+        h = _READERS.get(key)
+        if h is None:
+            if not _READERS:
+                # an interpreter exit with a reader open must not leave its
+                # threads inside the runtime while that is torn down
+                __import__("atexit").register(_close_readers)
+            h = ext.scan_open(threads, streams, int(piece_bytes))
+            if not h:
+                raise RuntimeError("hipdf scan_open failed")
+            _READERS[key] = h
+        return h
+
+
+def _stream_layout(table, files):
+    """What a stream scan of `files` uploads, from the footers alone: per
+    file its rows and one (column position, chunk offset, chunk bytes,
+    physical width, destination width, values, max def level) entry per
+    selected column chunk, or None when a chunk cannot be eligible (the page
+    headers are checked later, by the native walker). Cached per scan
+    shape, keyed on the files' mtimes like the footers."""
+    import os
+
+    from ..column import torch_dtype
+    from .parquet import _rg_keep, arrow_to_dtype
+
+    columns = [f.name for f in table.schema.fields]
+    pred = getattr(table, "rg_predicate", None)
+    key = (tuple(files), tuple(columns), repr(pred) if pred else None,
+           getattr(table, "chunk_bytes", 0))
+    mtimes = tuple(os.path.getmtime(p) for p in files)
+    hit = _STREAM_LAYOUTS.get(key)
+    if hit is not None and hit[0] == mtimes and not pred:
+        return hit[1]
+
+    def build():
+        dtypes = None
+        per_file = []
+        for path in files:
+            md, arrow_schema, pq_schema = _file_meta(path)
+            keep = _rg_keep(path, pred) if pred else None
+            if table._rg_chunks(path, keep) is not None:
+                return None  # read row group by row group: the old path
+            fdt = [arrow_to_dtype(arrow_schema.field(n).type)
+                   for n in columns]
+            if dtypes is None:
+                dtypes = fdt
+            elif [d.id for d in fdt] != [d.id for d in dtypes]:
+                return None
+            name_to_idx = {md.row_group(0).column(j).path_in_schema: j
+                           for j in range(md.num_columns)} \
+                if md.num_row_groups else {}
+            chunks = []
+            rows = 0
+            for rg in range(md.num_row_groups):
+                if keep is not None and rg not in keep:
+                    continue
+                rgmd = md.row_group(rg)
+                for ci, (name, dt) in enumerate(zip(columns, fdt)):
+                    j = name_to_idx.get(name)
+                    if j is None or dt.is_nested \
+                            or dt.id in (TypeId.STRING, TypeId.BOOL):
+                        return None
+                    sc = pq_schema.column(j)
+                    cmd = rgmd.column(j)
+                    pw = _PHYS_WIDTH.get(cmd.physical_type)
+                    dw = torch.empty(0, dtype=torch_dtype(dt)).element_size()
+                    # 4 -> 8 is the signed widen of INT32-physical decimals
+                    if pw is None or sc.max_repetition_level > 0 \
+                            or cmd.compression != "UNCOMPRESSED" \
+                            or cmd.has_dictionary_page \
+                            or not (dw == pw or (cmd.physical_type == "INT32"
+                                                 and dw == 8
+                                                 and dt.is_decimal)) \
+                            or cmd.num_values != rgmd.num_rows:
+                        return None
+                    chunks.append((ci, cmd.data_page_offset,
+                                   cmd.total_compressed_size, pw, dw,
+                                   cmd.num_values, sc.max_definition_level,
+                                   rows))
+                rows += rgmd.num_rows
+            per_file.append((rows, chunks))
+        if dtypes is None:
+            return None
+        return dtypes, per_file
+
+    layout = build()
+    if len(_STREAM_LAYOUTS) > 256:
+        _STREAM_LAYOUTS.clear()
+    _STREAM_LAYOUTS[key] = (mtimes, layout)
+    return layout
+
+
+class StreamScan:
+    """One running stream scan: the upload is submitted by start() and the
+    batches, one per group of files_per_batch files, are handed out by
+    batches() as their files complete.
+
+    Every destination buffer is allocated before the submit (the memory
+    rule in scan_reader.hip: the device pool ignores streams)."""
+
+    def __init__(self, reader: int, ticket: int, batches, keepalive):
+        self._reader = reader
+        self._ticket = ticket
+        self._batches = batches
+        self._keepalive = keepalive  # file mappings the workers read
+
+    @staticmethod
+    def start(table, files) -> Optional["StreamScan"]:
+        from ..column import torch_dtype
+        from ..ops.gpu_backend import _stream, ext
+        from .parquet import PHASE_STATS
+
+        layout = _stream_layout(table, files)
+        if layout is None:
+            return None
+        dtypes, per_file = layout
+        per_batch = max(1, int(getattr(table, "stream_files", 1)))
+        tdts = [torch_dtype(d) for d in dtypes]
+        batches = []
+        descs = []
+        keepalive = []
+        nbytes = 0
+        for g in range(0, len(files), per_batch):
+            group = per_file[g:g + per_batch]
+            rows = sum(r for r, _ in group)
+            bufs = [torch.empty(max(rows, 1), dtype=t, device="cuda")[:rows]
+                    for t in tdts]
+            base = 0
+            for path, (frows, chunks) in zip(files[g:g + per_batch], group):
+                mm = _file_mmap(path)
+                keepalive.append(mm)
+                for ci, off, nb, pw, dw, nvals, max_def, row0 in chunks:
+                    if off < 0 or off + nb > mm[3]:
+                        return None
+                    descs.append((mm[2] + off, nb, pw, dw,
+                                  bufs[ci].data_ptr() + (base + row0) * dw,
+                                  nvals, len(batches), max_def))
+                    nbytes += nvals * pw
+                base += frows
+            batches.append(ColumnBatch(
+                [Column(d, rows, b, None, null_count=0)
+                 for d, b in zip(dtypes, bufs)], rows))
+        table_np = np.array(descs, dtype=np.dtype(
+            [("src", "<i8"), ("nbytes", "<i8"), ("pw", "<i4"), ("dw", "<i4"),
+             ("dst", "<i8"), ("n", "<i8"), ("group", "<i4"),
+             ("max_def", "<i4")]))  # HipdfScanChunk
+        reader = _reader(table.prefetch_threads,
+                         getattr(table, "stream_piece_bytes", 0)
+                         or STREAM_PIECE_BYTES)
+        ticket = ext.scan_submit(reader, table_np.ctypes.data, len(descs),
+                                 len(batches), _stream())
+        if ticket <= 0:
+            if ticket <= -100:
+                raise RuntimeError(f"hipdf scan_submit failed rc={ticket}")
+            return None  # a page header the walker does not take
+        PHASE_STATS["upload_bytes"] += nbytes
+        return StreamScan(reader, ticket, batches, keepalive)
+
+    def batches(self):
+        from ..ops.gpu_backend import _stream, ext
+
+        try:
+            for g in range(len(self._batches)):
+                rc = ext.scan_wait_group(self._reader, self._ticket, g,
+                                         _stream())
+                if rc != 0:
+                    raise RuntimeError(f"stream scan failed rc={rc}")
+                batch, self._batches[g] = self._batches[g], None
+                yield batch
+        finally:
+            self.close()
+
+    def close(self):
+        """Ends the scan, consumed or not; pieces not yet claimed are never
+        copied. Safe to call twice."""
+        from ..ops.gpu_backend import ext
+
+        if self._ticket:
+            ticket, self._ticket = self._ticket, 0
+            ext.scan_cancel(self._reader, ticket)
+            self._batches = []
+            self._keepalive = []

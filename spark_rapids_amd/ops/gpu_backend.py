@@ -1934,8 +1934,16 @@ def gather_dict(batch: ColumnBatch, indices: Column,
     idx = indices.data
     if idx.numel() != n_out:
         idx = idx[:n_out]  # one tensor object: the views share their codes
-    return _gather_by_idx(batch, idx, n_out, maybe_negative=negatives,
-                          dict_strings=True)
+    out = _gather_by_idx(batch, idx, n_out, maybe_negative=negatives,
+                         dict_strings=True)
+    # a non-null integer column gathered without misses holds a subset of
+    # the build column's values: its range is found on the build column,
+    # once for all probe batches (see _key_minmax), not per batch
+    for src, c in zip(batch.columns, out.columns):
+        if c.validity is None and c.dtype.id in _DENSE_OK \
+                and not isinstance(c, DictColumn) and c.size:
+            c._minmax = src
+    return out
 
 
 def _gather_validity(c: Column, idx: torch.Tensor,
@@ -2051,6 +2059,9 @@ def _gather_by_idx(batch: ColumnBatch, idx: torch.Tensor, n_out: int,
         for ci, c, out, ov in outs:
             cols[ci] = Column(c.dtype, n_out, out, ov,
                               null_count=None if ov is not None else 0)
+            if ov is None:
+                # a subset of c's rows: a range known for c holds here too
+                cols[ci]._minmax = c._minmax
     return ColumnBatch(cols, n_out)
 
 
@@ -2507,7 +2518,25 @@ def _dict_group_table(dicts: List[Column], need_null_slot: bool):
     dictionary row r in [0, G), leaders[g] one dictionary row of group g.
     With a NULL slot, slot G stands for "every key NULL": rows coded -1 go
     there, and so do dictionary rows whose strings are all NULL, so that
-    both kinds of NULL key make one group (leaders[G] = -1)."""
+    both kinds of NULL key make one group (leaders[G] = -1).
+
+    The result is cached on the leading dictionary column: the dictionaries
+    are a join's build columns, the same objects for every probe batch, so a
+    dimension's key strings are grouped once per query and not once per
+    batch. The entry holds the other dictionaries, which keeps their ids
+    from being reused, and nothing writes to the tensors it returns."""
+    key = (tuple(id(c) for c in dicts), bool(need_null_slot))
+    cache = dicts[0]._group_tables
+    if cache is None:
+        cache = dicts[0]._group_tables = {}
+    hit = cache.get(key)
+    if hit is None:
+        hit = cache[key] = (list(dicts),
+                            _build_dict_group_table(dicts, need_null_slot))
+    return hit[1]
+
+
+def _build_dict_group_table(dicts: List[Column], need_null_slot: bool):
     d = dicts[0].size
     if d == 0:
         table = torch.zeros(0, dtype=torch.int32, device="cuda")
@@ -2524,6 +2553,27 @@ def _dict_group_table(dicts: List[Column], need_null_slot: bool):
         leaders = torch.cat([leaders, torch.full(
             (1,), -1, dtype=torch.int32, device="cuda")])
     return table, g, leaders, has_null_slot
+
+
+def _column_minmax(k: Column):
+    """(min, max) of a column: two reductions with a readback each."""
+    return reduce("min", k), reduce("max", k)
+
+
+def _key_minmax(k: Column):
+    """A range that holds every value of the non-null integer key `k`,
+    cached on the column: stored tables are re-scanned every query, and
+    columns are immutable by convention. A column that a join gathered from
+    its build side carries that build column in `_minmax` (gather_dict) and
+    takes its range, which is found once on the build column, at dimension
+    scale, however many probe batches there are. Such a range may be wider
+    than the key's own; the dense ids only need it to cover the values."""
+    mm = k._minmax
+    if isinstance(mm, Column):
+        mm = k._minmax = _key_minmax(mm)
+    elif mm is None:
+        mm = k._minmax = _column_minmax(k)
+    return mm
 
 
 def _try_dense_keys(keys, aggs, selp, n):
@@ -2550,11 +2600,7 @@ def _try_dense_keys(keys, aggs, selp, n):
                 comps.append(comp)
             comp[1].append(i)
             continue
-        if k._minmax is None:
-            # cached on the column: stored tables are re-scanned every
-            # query, and columns are immutable by convention
-            k._minmax = (reduce("min", k), reduce("max", k))
-        kmin, kmax = k._minmax
+        kmin, kmax = _key_minmax(k)
         if kmin is None:
             return None
         rng = int(kmax) - int(kmin) + 1

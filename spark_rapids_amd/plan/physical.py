@@ -99,12 +99,79 @@ class ScanExec(PhysicalExec):
         self.source = source
         self.label = label
 
+    # streaming: the running execution is a stream scan (io/parquet_gpu.py),
+    # whose batches are the scan's file groups and stay apart
+    streaming = False
+    # what start_stream_scan() found, until execute() takes it: None = not
+    # asked, False = the source has no stream scan for this one
+    _started = None
+    _running = None  # the stream scan execute() is pulling
+
+    def start_stream_scan(self) -> bool:
+        """Submit the scan's upload ahead of the first pull, when the source
+        has a stream scan for it. execute() picks the running scan up."""
+        if self._started is None:
+            start = getattr(self.source, "start_stream_scan", None)
+            scan = start() if self.gpu and start is not None else None
+            self._started = scan if scan is not None else False
+        return self._started is not False
+
+    def stop_stream_scan(self) -> None:
+        for scan in (self._started, self._running):
+            if scan:
+                scan.close()  # idempotent
+        self._started = self._running = None
+
     def execute(self) -> Iterator[ColumnBatch]:
-        for batch in self.source.partitions():
+        self.start_stream_scan()
+        scan, self._started = self._started, None
+        self.streaming = scan is not False
+        if scan is not False:
+            self._running = scan
+            batches = scan.batches()
+        elif hasattr(self.source, "partitions_per_file"):
+            batches = self.source.partitions_per_file()
+        else:
+            batches = self.source.partitions()
+        for batch in batches:
             yield batch.to(self.device)
 
     def describe(self):
         return f"{self.name()}({self.label})"
+
+
+def start_stream_scans(root: PhysicalExec) -> List[ScanExec]:
+    """Start every stream scan of a plan before its first exec is pulled:
+    the fact upload then runs under the dimension scans and hash builds
+    that a join executes before it first pulls its probe side. Returns the
+    scans that started, for stop_stream_scans."""
+    started: List[ScanExec] = []
+    seen = set()
+
+    def walk(e: PhysicalExec):
+        if id(e) in seen:
+            return
+        seen.add(id(e))
+        if isinstance(e, ScanExec):
+            try:
+                if e.start_stream_scan():
+                    started.append(e)
+            except BaseException:
+                stop_stream_scans(started)
+                raise
+        # a join executes its build side (the last child) first
+        for c in reversed(e.children):
+            walk(c)
+
+    walk(root)
+    return started
+
+
+def stop_stream_scans(started: List[ScanExec]) -> None:
+    """End the started scans that nothing pulled (an early LIMIT, an error);
+    a scan that ran to its end is already closed."""
+    for e in started:
+        e.stop_stream_scan()
 
 
 class DeviceTransferExec(PhysicalExec):
@@ -135,8 +202,14 @@ class CoalesceBatchesExec(PhysicalExec):
     def execute(self) -> Iterator[ColumnBatch]:
         pending: List[ColumnBatch] = []
         pending_bytes = 0
-        for batch in self.children[0].execute():
+        child = self.children[0]
+        for batch in child.execute():
             if batch.num_rows == 0:
+                continue
+            if getattr(child, "streaming", False):
+                # a stream scan's batches are its file groups: merging them
+                # again would make every exec above wait for the last file
+                yield batch
                 continue
             nb = batch.nbytes
             if pending and pending_bytes + nb > self.target_bytes:
