@@ -121,7 +121,25 @@ __global__ void k_i128_to_f64(const int64_t* __restrict__ in,
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     i128 v = load128(in, i);
-    out[i] = (double)v.hi * 18446744073709551616.0 + (double)v.lo;
+    bool neg = v.hi < 0;
+    i128 m = neg ? neg128(v) : v;
+    uint64_t hi = (uint64_t)m.hi, lo = m.lo;
+    double d;
+    if (hi == 0) {
+      d = (double)lo;  // u64 -> f64 is one correctly rounded step
+    } else {
+      // normalise the magnitude so bit 127 is set, keep the top 64 bits and
+      // fold everything below into a sticky bit: the sticky bit sits 10
+      // places under the double's rounding position, so one u64 -> f64
+      // conversion rounds the full 128-bit value correctly; the power-of-
+      // two scale is exact
+      int lz = __clzll((long long)hi);
+      uint64_t top = lz ? (hi << lz) | (lo >> (64 - lz)) : hi;
+      uint64_t rest = lz ? lo << lz : lo;
+      if (rest) top |= 1;
+      d = ldexp((double)top, 64 - lz);
+    }
+    out[i] = neg ? -d : d;
   }
 }
 
@@ -293,15 +311,21 @@ __global__ void k_dec64_mul_div(int is_div, const int64_t* __restrict__ a,
           while (m > 0) {
             int c = m > 18 ? 18 : m;
             u128 p = pow10_128(c);
-            if (q > u128_max / p) {
-              q = u128_max;  // forces the precision-overflow null below
+            // q*p + (p-1) must fit; past this limit the quotient is already
+            // beyond 10^38, so the row is a precision overflow: null it
+            // here, before any rounding can wrap the value back into range
+            if (q > (u128_max - (p - 1)) / p) {
+              ok = false;
               break;
             }
             q = q * p + (r * p) / den;
             r = (r * p) % den;
             m -= c;
           }
-          if (2 * r >= den) q += 1;  // HALF_UP on the magnitude
+          if (ok && 2 * r >= den) {  // HALF_UP on the magnitude
+            if (q == u128_max) ok = false;
+            else q += 1;
+          }
         }
         if (ok && q >= pow10_128(out_prec)) ok = false;
       }
@@ -462,21 +486,28 @@ __global__ void k_dec_mul_div_wide(int is_div, const int64_t* __restrict__ a,
             ok = false;
           } else {
             q = ((u128)p.w[1] << 64) | p.w[0];
-            if (last >= 5) q += 1;
+            if (last >= 5) {
+              if (q == ~(u128)0) ok = false;  // would wrap to a valid 0
+              else q += 1;
+            }
           }
         } else if (y == 0) {
           ok = false;
         } else {
           int m = shift;
+          bool den_fits = true;
           if (m < 0) {
-            // denominator gains the digits instead; y*10^-m must fit
-            for (int k = 0; k < -m && ok; ++k) {
-              if (y > ~(u128)0 / 10) ok = false;
+            // denominator gains the digits instead. Once y*10^-m passes
+            // 2^128 it is more than twice any i128 magnitude (and, as a
+            // multiple of 10, never exactly 2^128), so the quotient rounds
+            // to 0: q stays 0 and the row stays valid
+            for (int k = 0; k < -m && den_fits; ++k) {
+              if (y > ~(u128)0 / 10) den_fits = false;
               else y *= 10;
             }
             m = 0;
           }
-          if (ok) {
+          if (den_fits) {
             q = x / y;
             u128 r = x % y;
             const u128 q_lim = (~(u128)0 - 9) / 10;
@@ -497,7 +528,7 @@ __global__ void k_dec_mul_div_wide(int is_div, const int64_t* __restrict__ a,
               q = q * 10 + digit;
               r = lo;
             }
-            if (ok && 2 * r >= y) {
+            if (ok && r >= y - r) {  // 2r >= y without the u128 wrap
               // HALF_UP on the true remainder of the last digit
               if (q == ~(u128)0) ok = false;
               else q += 1;

@@ -2246,8 +2246,10 @@ def reduce(op: str, col: Column):
                                 "max": -2 ** 63, "count": 0}[op],
                          dtype=torch.int64, device="cuda")
     cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
-    if op == "count" and not col.dtype.is_fixed_width:
-        # count over STRING/nested: only the validity matters
+    if op == "count" and (not col.dtype.is_fixed_width
+                          or col.dtype.id is TypeId.DECIMAL128):
+        # count over STRING/nested/decimal128 (two words a row, no typed
+        # accumulator): only the validity matters
         nn8 = torch.ones(max(n, 1), dtype=torch.uint8, device="cuda")[:n]
         col = Column(DType.bool_(), n, nn8, col.validity,
                      null_count=col._null_count)
@@ -2395,9 +2397,12 @@ def group_by_aggregate(batch: ColumnBatch, key_idx: List[int],
                                  op == "max", s)
             allocs.append(("collect", out_dtype, False, col, None, 0))
             continue
-        if op == "count" and vc is not None and not vc.dtype.is_fixed_width:
-            # count over STRING/nested only needs the validity: swap in a
-            # u8 non-null indicator column so no typed accumulator is hit
+        if op == "count" and vc is not None and (
+                not vc.dtype.is_fixed_width
+                or vc.dtype.id is TypeId.DECIMAL128):
+            # count over STRING/nested/decimal128 only needs the validity:
+            # swap in a u8 non-null indicator column so no typed
+            # accumulator is hit
             nn8 = torch.ones(max(vc.size, 1), dtype=torch.uint8,
                              device="cuda")[:vc.size]
             vc = Column(DType.bool_(), vc.size, nn8, vc.validity,
