@@ -572,4 +572,14 @@ PYBIND11_MODULE(hipdf, m) {
   BIND(list_find);
   BIND(list_slice_ranges);
   BIND(list_slice_map);
+  BIND(list_interleave);
+  BIND(list_interleave_map);
+  BIND(list_concat_lens);
+  BIND(list_concat_map);
+  BIND(list_flatten);
+  BIND(sequence_ranges);
+  BIND(sequence_fill);
+  BIND(array_join_sizes);
+  BIND(array_join_rows);
+  BIND(array_join_write);
 }

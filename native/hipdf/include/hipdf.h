@@ -767,6 +767,96 @@ void hipdf_list_slice_map(const void* new_offs, const void* src_start,
                           int64_t n, void* idx, int64_t total,
                           hipStream_t stream);
 
+/* ---- array builders: array(), concat, flatten, sequence, array_join ---- */
+/* Up to 8 per-row operands of one launch. Unlike the descriptor structs
+ * above this one is read from HOST memory by the entry point and handed to
+ * the kernel by value; more operands take more launches. Unused slots are
+ * NULL. a[j]: operand j's values (list_interleave) or int32 offsets[n + 1]
+ * (list_concat_*); valid[j]: its validity words or NULL. */
+#define HIPDF_LIST_MAX_OPERANDS 8
+typedef struct {
+  const void* a[HIPDF_LIST_MAX_OPERANDS];
+  const void* valid[HIPDF_LIST_MAX_OPERANDS];
+} HipdfListOperands;
+HIPDF_STATIC_ASSERT(sizeof(HipdfListOperands) == 128, "packed as <16q");
+/* array(c_0 .. c_{k-1}) over fixed-width operands of esize (1/2/4/8) bytes,
+ * n rows each, n * k <= INT32_MAX: out[i * k + j] = c_j[i]. ops (host) holds
+ * operands j0 .. j0 + kk - 1 of the k. vout: validity words covering n * k
+ * elements, or NULL when no operand has a mask. shared == 0: every operand
+ * is in this launch and each word is stored whole; shared == 1: the caller
+ * has zeroed vout and the launches OR their bits in. new_offs: int32[n + 1],
+ * i * k, or NULL. */
+void hipdf_list_interleave(int esize, const void* ops, int k, int j0, int kk,
+                           int shared, void* out, void* vout, void* new_offs,
+                           int64_t n, hipStream_t stream);
+/* the same layout as a gather map over the concatenation of the k operand
+ * columns: idx[i * k + j] = j * n + i (int32[n * k]); new_offs as above */
+void hipdf_list_interleave_map(int k, void* idx, void* new_offs, int64_t n,
+                               hipStream_t stream);
+/* concat of k LIST columns, row lengths. Launches go over the operands in
+ * order, kk (<= 8) at a time, first / last marking the outer ones. out_len:
+ * int64[n + 1], the running and after the last launch the final length, 0
+ * for a row that is null in any operand, entry n is 0; prefix: int32[n] or
+ * NULL, the running length before this launch's operands; vout: validity
+ * words covering n rows, the AND of the operands' */
+void hipdf_list_concat_lens(const void* ops, int kk, int first, int last,
+                            void* out_len, void* prefix, void* vout,
+                            int64_t n, hipStream_t stream);
+/* concat's gather map for the operands of one launch: new_offs int32[n + 1]
+ * from 0 to total; prefix as written by list_concat_lens for the same
+ * operands (NULL for the first launch); cbase (host): int64[kk], row of the
+ * concatenated children at which each operand's child begins. Writes
+ * idx[p] (int32[total]) for the elements that come from these operands. */
+void hipdf_list_concat_map(const void* ops, const void* cbase, int kk,
+                           const void* new_offs, const void* prefix,
+                           int64_t n, void* idx, int64_t total,
+                           hipStream_t stream);
+/* flatten(LIST<LIST<T>>), n >= 1 rows, w lanes (8/16/32/64) per row. outer /
+ * rvalid: the outer offsets and validity; inner / ivalid: the inner LIST
+ * column's. new_offs: int32[n + 1] = inner[outer[i]] - inner[outer[0]];
+ * vout: validity words covering n rows, bit = outer row valid and no inner
+ * array of the row null; span: int64[2] = inner[outer[0]], inner[outer[n]] */
+void hipdf_list_flatten(const void* outer, const void* rvalid,
+                        const void* inner, const void* ivalid, int w,
+                        void* new_offs, void* vout, void* span, int64_t n,
+                        hipStream_t stream);
+/* sequence(start, stop[, step]) per row, t = HIPDF_I32 or HIPDF_I64 for all
+ * three; step == NULL stands for 1 where start <= stop, else -1. out_len:
+ * int64[n + 1] elements per row (1 + (stop - start) / step, capped at 2^31),
+ * 0 for a null or an illegal row, entry n is 0; vout: validity words
+ * covering n rows; err: int64[4], err[0] preset to INT64_MAX: the least
+ * illegal row (start != stop and step == 0 or pointing away from stop) and
+ * its start, stop and step */
+void hipdf_sequence_ranges(int t, const void* start, const void* avalid,
+                           const void* stop, const void* bvalid,
+                           const void* step, const void* svalid,
+                           void* out_len, void* vout, void* err, int64_t n,
+                           hipStream_t stream);
+/* out[p] = start[row] + (p - offs[row]) * step[row]; offs int32[n + 1] from
+ * 0 to total */
+void hipdf_sequence_fill(int t, const void* offs, const void* start,
+                         const void* stop, const void* step, int64_t n,
+                         void* out, int64_t total, hipStream_t stream);
+/* array_join(LIST<STRING>, delimiter[, replacement]) in three passes around
+ * two scans. offsets / rvalid: the list; eoffs / bytes / cvalid: its string
+ * child; total = offsets[n] - offsets[0]; dlen: delimiter bytes; rlen:
+ * replacement bytes, -1 for none (null elements are skipped).
+ * sizes: contrib int64[total + 1], bytes each element adds with its
+ * delimiter, entry total is 0. rows: out_len int64[n + 1] from the exclusive
+ * scan of contrib. write: out_off is the exclusive scan of out_len. */
+void hipdf_array_join_sizes(const void* offsets, const void* rvalid,
+                            const void* eoffs, const void* cvalid, int dlen,
+                            int rlen, int64_t n, void* contrib, int64_t total,
+                            hipStream_t stream);
+void hipdf_array_join_rows(const void* offsets, const void* scanned, int dlen,
+                           int64_t n, void* out_len, hipStream_t stream);
+void hipdf_array_join_write(const void* offsets, const void* rvalid,
+                            const void* eoffs, const void* bytes,
+                            const void* cvalid, const void* delim, int dlen,
+                            const void* repl, int rlen, const void* scanned,
+                            const void* out_off, int64_t n, void* out,
+                            int64_t total, hipStream_t stream);
+
 /* ---- native in-order scan reader (scan_reader.hip) --------------------- */
 /* Host-only walk of one parquet column chunk: one (value offset from the
  * chunk start, value bytes, values) int64 triple per data page into out

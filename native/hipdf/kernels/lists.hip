@@ -694,6 +694,385 @@ __global__ void k_list_slice_map(const int32_t* __restrict__ new_offs,
   }
 }
 
+// ---- builders ------------------------------------------------------------
+// array() / concat / flatten / sequence / array_join (reference analogue:
+// GpuCreateArray in complexTypeCreator.scala, GpuConcat, GpuFlatten,
+// GpuSequence and GpuArrayJoin in collectionOperations.scala). These make
+// arrays, or a string per array, out of per-row operands. A launch takes up
+// to HIPDF_LIST_MAX_OPERANDS operands by value in a HipdfListOperands; its
+// pointers are picked with an unrolled compare, never by a run-time index,
+// so the struct stays in kernel-argument registers.
+
+constexpr int LIST_OPS = HIPDF_LIST_MAX_OPERANDS;
+
+template <typename P>
+__device__ __forceinline__ P pick_operand(const void* const (&a)[LIST_OPS],
+                                          int j) {
+  const void* p = a[0];
+#pragma unroll
+  for (int q = 1; q < LIST_OPS; ++q)
+    if (j == q) p = a[q];
+  return (P)p;
+}
+
+// array(c_0 .. c_{k-1}) over fixed-width operands: out[i * k + j] = c_j[i].
+// This launch holds operands j0 .. j0 + kk - 1. One thread per output
+// element of the whole result, so neighbouring lanes store neighbouring
+// elements; an element of another launch's operand is left alone. A wave
+// owns the 64 outputs of one validity word. With every operand in one launch
+// (shared == 0) it stores the word whole from its ballot; otherwise the
+// caller has zeroed the mask and the wave ORs its bits in. vout may be null
+// when no operand has a validity mask. new_offs (may be null): the result's
+// offsets, new_offs[i] = i * k for i in 0..n.
+template <typename T>
+__global__ __launch_bounds__(HIPDF_BLOCK) void k_list_interleave(
+    HipdfListOperands ops, int k, int j0, int kk, int shared,
+    T* __restrict__ out, uint64_t* __restrict__ vout,
+    int32_t* __restrict__ new_offs, int64_t n) {
+  int lane = lane_id();
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
+  int64_t total = n * k;  // <= INT32_MAX, the caller checks
+  if (new_offs)
+    for (int64_t i = tid; i <= n; i += nthreads) new_offs[i] = (int32_t)(i * k);
+  // wave-uniform bounds: every lane reaches the ballot
+  for (int64_t base = tid - lane; base < total; base += nthreads) {
+    int64_t p = base + lane;
+    bool bit = false;
+    if (p < total) {
+      uint32_t i = (uint32_t)p / (uint32_t)k;
+      int j = (int)((uint32_t)p - i * (uint32_t)k) - j0;
+      if (j >= 0 && j < kk) {
+        out[p] = pick_operand<const T*>(ops.a, j)[i];
+        bit = valid_bit(pick_operand<const uint64_t*>(ops.valid, j), i);
+      }
+    }
+    uint64_t bal = __ballot(bit);
+    if (vout && lane == 0) {
+      if (!shared) vout[base >> 6] = bal;
+      else if (bal) atomicOr((unsigned long long*)&vout[base >> 6],
+                             (unsigned long long)bal);
+    }
+  }
+}
+
+// The same layout as a gather map, for operands that move through the
+// gather (strings, decimal128): idx[i * k + j] = j * n + i indexes the
+// concatenation of the k operand columns.
+__global__ void k_list_interleave_map(int k, int32_t* __restrict__ idx,
+                                      int32_t* __restrict__ new_offs,
+                                      int64_t n) {
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
+  int64_t total = n * k;
+  for (int64_t i = tid; i <= n; i += nthreads) new_offs[i] = (int32_t)(i * k);
+  for (int64_t p = tid; p < total; p += nthreads) {
+    uint32_t i = (uint32_t)p / (uint32_t)k;
+    uint32_t j = (uint32_t)p - i * (uint32_t)k;
+    idx[p] = (int32_t)((int64_t)j * n + i);
+  }
+}
+
+// concat(a_0 .. a_{k-1}) per-row lengths, operands j0.. of this launch in
+// ops (a = int32 offsets[n + 1], valid = row validity). One lane per row and
+// one wave per 64-row stripe, rows 0..n (entry n of out_len is 0). The first
+// launch starts the running length and the validity word, a later one reads
+// what the launches before it left; prefix (may be null) receives the
+// running length BEFORE this launch's operands, which is where they start
+// inside the result row. The last launch zeroes the length of a row that is
+// null in any operand, so that out_len scans into the offsets.
+__global__ __launch_bounds__(HIPDF_BLOCK) void k_list_concat_lens(
+    HipdfListOperands ops, int kk, int first, int last,
+    int64_t* __restrict__ out_len, int32_t* __restrict__ prefix,
+    uint64_t* __restrict__ vout, int64_t n) {
+  int lane = lane_id();
+  int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  int64_t nwaves = (int64_t)gridDim.x * blockDim.x / WAVE;
+  int64_t nstripes = (n + 1 + WAVE - 1) / WAVE;
+  for (int64_t stripe = wave; stripe < nstripes; stripe += nwaves) {
+    int64_t row = stripe * WAVE + lane;
+    bool live = row < n;
+    int64_t sum = 0;
+    if (row < n) {
+#pragma unroll
+      for (int j = 0; j < LIST_OPS; ++j) {
+        if (j >= kk) continue;
+        const int32_t* o = (const int32_t*)ops.a[j];
+        sum += (int64_t)o[row + 1] - o[row];
+        live = live && valid_bit((const uint64_t*)ops.valid[j], row);
+      }
+    }
+    bool has_word = stripe * WAVE < n;  // the closing entry may stand alone
+    uint64_t word = __ballot(live);
+    if (!first && has_word) word &= vout[stripe];
+    int64_t prev = (first || row >= n) ? 0 : out_len[row];
+    if (prefix && row < n) prefix[row] = (int32_t)prev;
+    int64_t tot = prev + sum;
+    if (last && !((word >> lane) & 1ull)) tot = 0;
+    if (row <= n) out_len[row] = row < n ? tot : 0;
+    if (lane == 0 && has_word) vout[stripe] = word;
+  }
+}
+
+// gather map of concat, one thread per output element p: new_offs are the
+// result's offsets (from 0), prefix[row] (null = 0) the place in the result
+// row where this launch's operands begin, cbase.a[j] (an integer carried in
+// the pointer slot) the row of the concatenated children at which operand
+// j's child starts. An element that belongs to another launch's operands is
+// left alone.
+struct ListBases { int64_t b[LIST_OPS]; };
+
+__global__ void k_list_concat_map(HipdfListOperands ops, ListBases cbase,
+                                  int kk, const int32_t* __restrict__ new_offs,
+                                  const int32_t* __restrict__ prefix,
+                                  int64_t n, int32_t* __restrict__ idx,
+                                  int64_t total) {
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total;
+       p += (int64_t)gridDim.x * blockDim.x) {
+    int64_t row = row_of(new_offs, n, (int32_t)p);
+    int32_t r = (int32_t)p - new_offs[row] - (prefix ? prefix[row] : 0);
+    if (r < 0) continue;
+#pragma unroll
+    for (int j = 0; j < LIST_OPS; ++j) {
+      if (j >= kk || r < 0) continue;
+      const int32_t* o = (const int32_t*)ops.a[j];
+      int32_t b = o[row], len = o[row + 1] - b;
+      if (r < len) {
+        idx[p] = (int32_t)(cbase.b[j] + b + r);
+        r = -1;  // placed
+      } else {
+        r -= len;
+      }
+    }
+  }
+}
+
+// flatten(LIST<LIST<T>>): the new offsets index the innermost child,
+// new_offs[i] = inner[outer[i]] - inner[outer[0]] for i in 0..n. A row is
+// valid when the outer row is and none of its inner arrays is null. W lanes
+// stride over a row's inner arrays; stripes and the word write are
+// k_list_bool_reduce's. span[0] / span[1] receive the first and the closing
+// innermost index, which the host needs to cut the child.
+template <int W>
+__global__ __launch_bounds__(HIPDF_BLOCK) void k_list_flatten(
+    const int32_t* __restrict__ outer, const uint64_t* __restrict__ rvalid,
+    const int32_t* __restrict__ inner, const uint64_t* __restrict__ ivalid,
+    int32_t* __restrict__ new_offs, uint64_t* __restrict__ vout,
+    int64_t* __restrict__ span, int64_t n) {
+  constexpr int L = WAVE / W;  // rows per step
+  int lane = lane_id();
+  int sub = lane / W, sl = lane & (W - 1);
+  int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t wave = tid / WAVE;
+  int64_t nwaves = (int64_t)gridDim.x * blockDim.x / WAVE;
+  int64_t nstripes = (n + WAVE - 1) / WAVE;
+  int32_t base = inner[outer[0]];
+  if (tid == 0) {
+    span[0] = base;
+    span[1] = inner[outer[n]];
+    new_offs[n] = inner[outer[n]] - base;
+  }
+  // loop bounds are wave-uniform: every lane reaches every shuffle / ballot
+  for (int64_t stripe = wave; stripe < nstripes; stripe += nwaves) {
+    uint64_t word = 0;
+    for (int step = 0; step < W; ++step) {
+      int64_t row = stripe * WAVE + step * L + sub;
+      bool rv = row < n && valid_bit(rvalid, row);
+      int32_t start = 0, len = 0;
+      if (row < n) {
+        start = outer[row];
+        if (sl == 0) new_offs[row] = inner[start] - base;
+        if (rv && ivalid) len = outer[row + 1] - start;
+      }
+      int bad = 0;
+      for (int32_t i = sl; i < len; i += W)
+        if (!valid_bit(ivalid, start + i)) bad = 1;
+#pragma unroll
+      for (int j = W >> 1; j > 0; j >>= 1) bad |= __shfl_xor(bad, j, W);
+      uint64_t bal = __ballot(rv && !bad && sl == 0);
+#pragma unroll
+      for (int g = 0; g < L; ++g)
+        word |= ((bal >> (g * W)) & 1ull) << (step * L + g);
+    }
+    if (lane == 0) vout[stripe] = word;
+  }
+}
+
+// sequence(start, stop[, step]) per row: lengths, validity and the error
+// record. T is int32_t or int64_t, U its unsigned twin; step == null means
+// 1 when start <= stop, else -1. A row is live when every operand is
+// non-null. start == stop has one element whatever the step; otherwise a
+// zero step, or one that points away from stop, is an error. The distance
+// and the step's magnitude are taken in U, where stop - start cannot
+// overflow, and the length is capped at 2^31 so that n of them cannot
+// overflow the int64 scan (anything above INT32_MAX is refused by the host
+// anyway). out_len: int64[n + 1], 0 for a row that is not live or is in
+// error, entry n is 0. err[0] (preset to INT64_MAX by the caller) becomes
+// the least row index in error.
+template <typename T, typename U>
+__global__ __launch_bounds__(HIPDF_BLOCK) void k_sequence_ranges(
+    const T* __restrict__ start, const uint64_t* __restrict__ avalid,
+    const T* __restrict__ stop, const uint64_t* __restrict__ bvalid,
+    const T* __restrict__ step, const uint64_t* __restrict__ svalid,
+    int64_t* __restrict__ out_len, uint64_t* __restrict__ vout,
+    long long* __restrict__ err, int64_t n) {
+  int lane = lane_id();
+  int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+  int64_t nwaves = (int64_t)gridDim.x * blockDim.x / WAVE;
+  int64_t nstripes = (n + 1 + WAVE - 1) / WAVE;
+  for (int64_t stripe = wave; stripe < nstripes; stripe += nwaves) {
+    int64_t row = stripe * WAVE + lane;
+    bool live = row < n && valid_bit(avalid, row) && valid_bit(bvalid, row) &&
+                (!step || valid_bit(svalid, row));
+    int64_t len = 0;
+    bool bad = false;
+    if (live) {
+      T a = start[row], b = stop[row];
+      T st = step ? step[row] : (a <= b ? (T)1 : (T)-1);
+      if (a == b) {
+        len = 1;
+      } else if (st == 0 || (b > a) != (st > 0)) {
+        bad = true;
+      } else {
+        U dist = b > a ? (U)b - (U)a : (U)a - (U)b;
+        U mag = st > 0 ? (U)st : (U)0 - (U)st;
+        U q = dist / mag;
+        len = q >= (U)0x7fffffff ? (int64_t)1 << 31 : (int64_t)q + 1;
+      }
+    }
+    if (row <= n) out_len[row] = len;
+    uint64_t bal = __ballot(live);
+    uint64_t bb = __ballot(bad);
+    if (lane == 0) {
+      if (stripe * WAVE < n) vout[stripe] = bal;
+      if (bb) atomicMin(&err[0], (long long)(stripe * WAVE + __ffsll((unsigned long long)bb) - 1));
+    }
+  }
+}
+
+// completes the error record after k_sequence_ranges (same stream): err[1..3]
+// = start, stop and step of row err[0], when there is one
+template <typename T>
+__global__ void k_sequence_err_values(const T* __restrict__ start,
+                                      const T* __restrict__ stop,
+                                      const T* __restrict__ step,
+                                      long long* __restrict__ err, int64_t n) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  long long row = err[0];
+  if (row < 0 || row >= n) return;
+  T a = start[row], b = stop[row];
+  err[1] = a;
+  err[2] = b;
+  err[3] = step ? step[row] : (a <= b ? (T)1 : (T)-1);
+}
+
+// out[p] = start[row] + (p - offs[row]) * step[row] for the row that owns
+// element p; offs from 0. The product is formed in U: it may pass through
+// values T cannot hold, the sum never leaves T's range.
+template <typename T, typename U>
+__global__ void k_sequence_fill(const int32_t* __restrict__ offs,
+                                const T* __restrict__ start,
+                                const T* __restrict__ stop,
+                                const T* __restrict__ step, int64_t n,
+                                T* __restrict__ out, int64_t total) {
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total;
+       p += (int64_t)gridDim.x * blockDim.x) {
+    int64_t row = row_of(offs, n, (int32_t)p);
+    T a = start[row];
+    T st = step ? step[row] : (a <= stop[row] ? (T)1 : (T)-1);
+    out[p] = (T)((U)a + (U)((int32_t)p - offs[row]) * (U)st);
+  }
+}
+
+// array_join(LIST<STRING>, delimiter[, replacement]), element-parallel.
+// Sizes: contrib[p] for element (offsets[0] + p) is its byte length (the
+// replacement's for a null element when there is one) plus the delimiter's,
+// 0 for a skipped null and all over a null row; entry `total` is 0. After
+// the exclusive scan S of contrib, a row over elements [a, b) holds
+// S[b] - S[a] bytes less one delimiter (when that is not 0), and an element
+// is the row's first emitted one exactly when S[p] == S[a]: if an emitted
+// element before it contributed nothing, the delimiter is empty and the
+// difference is nothing to write.
+__global__ void k_array_join_sizes(const int32_t* __restrict__ offsets,
+                                   const uint64_t* __restrict__ rvalid,
+                                   const int32_t* __restrict__ eoffs,
+                                   const uint64_t* __restrict__ cvalid,
+                                   int32_t dlen, int32_t rlen, int64_t n,
+                                   int64_t* __restrict__ contrib,
+                                   int64_t total) {
+  int32_t off0 = offsets[0];
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p <= total;
+       p += (int64_t)gridDim.x * blockDim.x) {
+    int64_t c = 0;
+    if (p < total) {
+      int32_t gi = off0 + (int32_t)p;
+      int64_t row = row_of(offsets, n, gi);
+      if (valid_bit(rvalid, row)) {
+        if (valid_bit(cvalid, gi)) c = (int64_t)(eoffs[gi + 1] - eoffs[gi]) + dlen;
+        else if (rlen >= 0) c = (int64_t)rlen + dlen;
+      }
+    }
+    contrib[p] = c;
+  }
+}
+
+// row byte lengths from the scan S (int64[total + 1]); entry n is 0
+__global__ void k_array_join_rows(const int32_t* __restrict__ offsets,
+                                  const int64_t* __restrict__ S, int32_t dlen,
+                                  int64_t n, int64_t* __restrict__ out_len) {
+  int32_t off0 = offsets[0];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    int64_t len = 0;
+    if (i < n) {
+      len = S[offsets[i + 1] - off0] - S[offsets[i] - off0];
+      if (len > 0) len -= dlen;
+    }
+    out_len[i] = len;
+  }
+}
+
+// write pass, one thread per element: the delimiter unless the element is
+// the first emitted one of its row, then the element's (or replacement's)
+// bytes. out_off: int64 byte offset of every row in out.
+__global__ void k_array_join_write(const int32_t* __restrict__ offsets,
+                                   const uint64_t* __restrict__ rvalid,
+                                   const int32_t* __restrict__ eoffs,
+                                   const uint8_t* __restrict__ bytes,
+                                   const uint64_t* __restrict__ cvalid,
+                                   const uint8_t* __restrict__ delim,
+                                   int32_t dlen,
+                                   const uint8_t* __restrict__ repl,
+                                   int32_t rlen, const int64_t* __restrict__ S,
+                                   const int64_t* __restrict__ out_off,
+                                   int64_t n, uint8_t* __restrict__ out,
+                                   int64_t total) {
+  int32_t off0 = offsets[0];
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total;
+       p += (int64_t)gridDim.x * blockDim.x) {
+    if (S[p + 1] == S[p] && dlen > 0) continue;  // nothing emitted here
+    int32_t gi = off0 + (int32_t)p;
+    int64_t row = row_of(offsets, n, gi);
+    if (!valid_bit(rvalid, row)) continue;
+    const uint8_t* src;
+    int32_t len;
+    if (valid_bit(cvalid, gi)) {
+      src = bytes + eoffs[gi];
+      len = eoffs[gi + 1] - eoffs[gi];
+    } else if (rlen >= 0) {
+      src = repl;
+      len = rlen;
+    } else {
+      continue;
+    }
+    int64_t within = S[p] - S[offsets[row] - off0];
+    uint8_t* dst = out + out_off[row] + within;
+    if (within > 0)
+      for (int32_t b = 0; b < dlen; ++b) dst[b - dlen] = delim[b];
+    for (int32_t b = 0; b < len; ++b) dst[b] = src[b];
+  }
+}
+
 // ---- host side -----------------------------------------------------------
 
 template <typename F>
@@ -909,6 +1288,159 @@ void hipdf_list_slice_map(const void* new_offs, const void* src_start,
   hipLaunchKernelGGL(k_list_slice_map, flat_grid(total), dim3(HIPDF_BLOCK), 0,
                      stream, (const int32_t*)new_offs,
                      (const int32_t*)src_start, n, (int32_t*)idx, total);
+}
+
+static inline int list_operand_count(int kk) {
+  if (kk < 1 || kk > LIST_OPS)
+    throw std::runtime_error("hipdf: 1 to 8 list operands per launch");
+  return kk;
+}
+
+void hipdf_list_interleave(int esize, const void* ops, int k, int j0, int kk,
+                           int shared, void* out, void* vout, void* new_offs,
+                           int64_t n, hipStream_t stream) {
+  if (n <= 0) return;
+  list_operand_count(kk);
+  if (k < 1 || j0 < 0 || j0 + kk > k || n * (int64_t)k > INT32_MAX)
+    throw std::runtime_error("hipdf: list_interleave operand range");
+  HipdfListOperands o = *(const HipdfListOperands*)ops;  // host memory
+  auto launch = [&]<typename T>() {
+    hipLaunchKernelGGL((k_list_interleave<T>), flat_grid(n * k),
+                       dim3(HIPDF_BLOCK), 0, stream, o, k, j0, kk, shared,
+                       (T*)out, (uint64_t*)vout, (int32_t*)new_offs, n);
+  };
+  switch (esize) {
+    case 1: launch.template operator()<uint8_t>(); break;
+    case 2: launch.template operator()<uint16_t>(); break;
+    case 4: launch.template operator()<uint32_t>(); break;
+    case 8: launch.template operator()<uint64_t>(); break;
+    default: throw std::runtime_error("hipdf: list_interleave element size");
+  }
+}
+
+void hipdf_list_interleave_map(int k, void* idx, void* new_offs, int64_t n,
+                               hipStream_t stream) {
+  if (n <= 0) return;
+  if (k < 1 || n * (int64_t)k > INT32_MAX)
+    throw std::runtime_error("hipdf: list_interleave_map operand count");
+  hipLaunchKernelGGL(k_list_interleave_map, flat_grid(n * k),
+                     dim3(HIPDF_BLOCK), 0, stream, k, (int32_t*)idx,
+                     (int32_t*)new_offs, n);
+}
+
+void hipdf_list_concat_lens(const void* ops, int kk, int first, int last,
+                            void* out_len, void* prefix, void* vout,
+                            int64_t n, hipStream_t stream) {
+  if (n <= 0) return;
+  list_operand_count(kk);
+  HipdfListOperands o = *(const HipdfListOperands*)ops;  // host memory
+  hipLaunchKernelGGL(k_list_concat_lens, stripe_grid(n + 1),
+                     dim3(HIPDF_BLOCK), 0, stream, o, kk, first, last,
+                     (int64_t*)out_len, (int32_t*)prefix, (uint64_t*)vout, n);
+}
+
+void hipdf_list_concat_map(const void* ops, const void* cbase, int kk,
+                           const void* new_offs, const void* prefix,
+                           int64_t n, void* idx, int64_t total,
+                           hipStream_t stream) {
+  if (n <= 0 || total <= 0) return;
+  list_operand_count(kk);
+  HipdfListOperands o = *(const HipdfListOperands*)ops;  // host memory
+  ListBases b{};
+  for (int j = 0; j < kk; ++j) b.b[j] = ((const int64_t*)cbase)[j];
+  hipLaunchKernelGGL(k_list_concat_map, flat_grid(total), dim3(HIPDF_BLOCK),
+                     0, stream, o, b, kk, (const int32_t*)new_offs,
+                     (const int32_t*)prefix, n, (int32_t*)idx, total);
+}
+
+void hipdf_list_flatten(const void* outer, const void* rvalid,
+                        const void* inner, const void* ivalid, int w,
+                        void* new_offs, void* vout, void* span, int64_t n,
+                        hipStream_t stream) {
+  if (n <= 0) return;
+  int64_t waves = (n + WAVE - 1) / WAVE;  // one wave per 64-row stripe
+  dispatch_width(w, [&]<int W>() {
+    hipLaunchKernelGGL((k_list_flatten<W>), flat_grid(waves * WAVE),
+                       dim3(HIPDF_BLOCK), 0, stream, (const int32_t*)outer,
+                       (const uint64_t*)rvalid, (const int32_t*)inner,
+                       (const uint64_t*)ivalid, (int32_t*)new_offs,
+                       (uint64_t*)vout, (int64_t*)span, n);
+  });
+}
+
+void hipdf_sequence_ranges(int t, const void* start, const void* avalid,
+                           const void* stop, const void* bvalid,
+                           const void* step, const void* svalid,
+                           void* out_len, void* vout, void* err, int64_t n,
+                           hipStream_t stream) {
+  if (n <= 0) return;
+  auto launch = [&]<typename T, typename U>() {
+    hipLaunchKernelGGL((k_sequence_ranges<T, U>), stripe_grid(n + 1),
+                       dim3(HIPDF_BLOCK), 0, stream, (const T*)start,
+                       (const uint64_t*)avalid, (const T*)stop,
+                       (const uint64_t*)bvalid, (const T*)step,
+                       (const uint64_t*)svalid, (int64_t*)out_len,
+                       (uint64_t*)vout, (long long*)err, n);
+    hipLaunchKernelGGL((k_sequence_err_values<T>), dim3(1), dim3(WAVE), 0,
+                       stream, (const T*)start, (const T*)stop,
+                       (const T*)step, (long long*)err, n);
+  };
+  if (t == HT_I32) launch.template operator()<int32_t, uint32_t>();
+  else if (t == HT_I64) launch.template operator()<int64_t, uint64_t>();
+  else throw std::runtime_error("hipdf: sequence needs int32 or int64");
+}
+
+void hipdf_sequence_fill(int t, const void* offs, const void* start,
+                         const void* stop, const void* step, int64_t n,
+                         void* out, int64_t total, hipStream_t stream) {
+  if (n <= 0 || total <= 0) return;
+  auto launch = [&]<typename T, typename U>() {
+    hipLaunchKernelGGL((k_sequence_fill<T, U>), flat_grid(total),
+                       dim3(HIPDF_BLOCK), 0, stream, (const int32_t*)offs,
+                       (const T*)start, (const T*)stop, (const T*)step, n,
+                       (T*)out, total);
+  };
+  if (t == HT_I32) launch.template operator()<int32_t, uint32_t>();
+  else if (t == HT_I64) launch.template operator()<int64_t, uint64_t>();
+  else throw std::runtime_error("hipdf: sequence needs int32 or int64");
+}
+
+void hipdf_array_join_sizes(const void* offsets, const void* rvalid,
+                            const void* eoffs, const void* cvalid, int dlen,
+                            int rlen, int64_t n, void* contrib, int64_t total,
+                            hipStream_t stream) {
+  if (n <= 0 || total < 0) return;
+  hipLaunchKernelGGL(k_array_join_sizes, flat_grid(total + 1),
+                     dim3(HIPDF_BLOCK), 0, stream, (const int32_t*)offsets,
+                     (const uint64_t*)rvalid, (const int32_t*)eoffs,
+                     (const uint64_t*)cvalid, (int32_t)dlen, (int32_t)rlen, n,
+                     (int64_t*)contrib, total);
+}
+
+void hipdf_array_join_rows(const void* offsets, const void* scanned, int dlen,
+                           int64_t n, void* out_len, hipStream_t stream) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_array_join_rows, flat_grid(n + 1), dim3(HIPDF_BLOCK),
+                     0, stream, (const int32_t*)offsets,
+                     (const int64_t*)scanned, (int32_t)dlen, n,
+                     (int64_t*)out_len);
+}
+
+void hipdf_array_join_write(const void* offsets, const void* rvalid,
+                            const void* eoffs, const void* bytes,
+                            const void* cvalid, const void* delim, int dlen,
+                            const void* repl, int rlen, const void* scanned,
+                            const void* out_off, int64_t n, void* out,
+                            int64_t total, hipStream_t stream) {
+  if (n <= 0 || total <= 0) return;
+  hipLaunchKernelGGL(k_array_join_write, flat_grid(total), dim3(HIPDF_BLOCK),
+                     0, stream, (const int32_t*)offsets,
+                     (const uint64_t*)rvalid, (const int32_t*)eoffs,
+                     (const uint8_t*)bytes, (const uint64_t*)cvalid,
+                     (const uint8_t*)delim, (int32_t)dlen,
+                     (const uint8_t*)repl, (int32_t)rlen,
+                     (const int64_t*)scanned, (const int64_t*)out_off, n,
+                     (uint8_t*)out, total);
 }
 
 }  // extern "C"

@@ -10,7 +10,8 @@ from __future__ import annotations
 import decimal
 import inspect
 import itertools
-from typing import Optional, Sequence
+from typing import Optional
+from typing import Sequence as _Seq
 
 import numpy as np
 
@@ -28,7 +29,7 @@ class Expression:
         return True
 
     @property
-    def children(self) -> Sequence["Expression"]:
+    def children(self) -> _Seq["Expression"]:
         return ()
 
     def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
@@ -139,8 +140,21 @@ class Expression:
         return UnaryExpr("rtrim", self)
 
     def concat(self, other) -> "BinaryExpr":
-        """Spark concat(): NULL if either side is NULL."""
+        """Spark concat(): NULL if either side is NULL. Strings join their
+        bytes; arrays of one type join their elements."""
         return BinaryExpr("concat", self, _as_expr(other))
+
+    def flatten(self) -> "Flatten":
+        """The inner arrays of this array<array<T>> value as one array<T>
+        (Spark flatten)."""
+        return Flatten(self)
+
+    def array_join(self, delimiter: str,
+                   null_replacement: Optional[str] = None) -> "ArrayJoin":
+        """The non-null strings of this array joined by `delimiter`; null
+        elements are skipped, or stand as `null_replacement` (Spark
+        array_join)."""
+        return ArrayJoin(self, delimiter, null_replacement)
 
     def replace(self, search: str, replacement: str) -> "RegexpReplace":
         """Literal substring replace (StringReplace analogue), lowered to
@@ -407,11 +421,33 @@ class BinaryExpr(Expression):
     def _in_dtype(self, schema) -> DType:
         return self._common(self.left.dtype(schema), self.right.dtype(schema))
 
+    def _array_concat(self, schema: Schema) -> Optional["ArrayConcat"]:
+        """concat is typed by its operands, which only the schema tells:
+        over arrays, the whole chain of nested concats (the SQL parser
+        folds concat(a, b, c) to the left) is one ArrayConcat; over
+        anything else this is None and the string path below stands."""
+        if self.op != "concat":
+            return None
+        leaves: list = []
+        todo = [self]
+        while todo:
+            e = todo.pop()
+            if isinstance(e, BinaryExpr) and e.op == "concat":
+                todo += (e.right, e.left)
+            else:
+                leaves.append(e)
+        if not any(e.dtype(schema).id is TypeId.LIST for e in leaves):
+            return None
+        return ArrayConcat(*leaves)
+
     def dtype(self, schema: Schema) -> DType:
         # NOTE: children's dtype() is called exactly once here — recursing
         # more than once makes deep expression chains exponential
         if self.op in _BOOL_OPS:
             return BOOL
+        arrays = self._array_concat(schema)
+        if arrays is not None:
+            return arrays.dtype(schema)
         lt, rt = self.left.dtype(schema), self.right.dtype(schema)
         if self.op in ("mul", "div") and _decimal_exact(lt, rt):
             # Spark DecimalPrecision rules: scale s1+s2 (mul) /
@@ -434,6 +470,9 @@ class BinaryExpr(Expression):
     _SWAP_CMP = {"lt": "gt", "gt": "lt", "le": "ge", "ge": "le"}
 
     def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
+        arrays = self._array_concat(schema)
+        if arrays is not None:
+            return arrays.eval(batch, schema)
         if self.op in ("mul", "div"):
             lt, rt = self.left.dtype(schema), self.right.dtype(schema)
             if _decimal_exact(lt, rt):
@@ -1179,6 +1218,232 @@ class ArrayRepeat(Expression):
         return f"array_repeat({self.child}, {self.count})"
 
 
+def _is_null_literal(e: Expression, schema: Schema) -> bool:
+    return isinstance(e, Literal) and e.value is None and \
+        e.dtype(schema).id is TypeId.NULL
+
+
+def _one_operand_type(fn: str, exprs, schema: Schema) -> DType:
+    """The one type all of `exprs` have; an untyped NULL literal takes it.
+    There is no implicit widening, as with the set operations."""
+    dt = None
+    for e in exprs:
+        if _is_null_literal(e, schema):
+            continue
+        t = e.dtype(schema)
+        if dt is None:
+            dt = t
+        elif t != dt:
+            raise TypeError(f"{fn} needs operands of one type, got {dt} "
+                            f"and {t}")
+    if dt is None:
+        raise TypeError(f"{fn} needs a typed operand; cast a NULL literal")
+    return dt
+
+
+def _typed_operands(exprs, dt: DType, schema: Schema):
+    return [Literal(None, dt) if _is_null_literal(e, schema) else e
+            for e in exprs]
+
+
+class CreateArray(Expression):
+    """array(e1, ..., ek): row i is [e1[i], ..., ek[i]]. The row is never
+    NULL; an element is null where its operand is. All operands have
+    exactly one type (GpuCreateArray analogue)."""
+
+    def __init__(self, *exprs):
+        if not exprs:
+            raise ValueError("array needs at least one operand")
+        self.exprs = tuple(_as_expr(e) for e in exprs)
+
+    @property
+    def children(self):
+        return self.exprs
+
+    def dtype(self, schema: Schema) -> DType:
+        return DType.list_(_one_operand_type("array", self.exprs, schema))
+
+    def nullable(self, schema: Schema) -> bool:
+        return False
+
+    def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
+        et = _one_operand_type("array", self.exprs, schema)
+        return ops.create_array(
+            [e.eval(batch, schema)
+             for e in _typed_operands(self.exprs, et, schema)])
+
+    def __str__(self):
+        return f"array({', '.join(str(e) for e in self.exprs)})"
+
+
+class ArrayConcat(Expression):
+    """concat(a1, ..., ak) over arrays of exactly one type: the rows'
+    elements in operand order, null elements kept; NULL when any operand
+    row is (GpuConcat analogue). `concat` over values whose types are only
+    known with the schema is a BinaryExpr, which hands its LIST case here."""
+
+    def __init__(self, *exprs):
+        if not exprs:
+            raise ValueError("concat needs at least one operand")
+        self.exprs = tuple(_as_expr(e) for e in exprs)
+
+    @property
+    def children(self):
+        return self.exprs
+
+    def dtype(self, schema: Schema) -> DType:
+        dt = _one_operand_type("concat", self.exprs, schema)
+        if dt.id is not TypeId.LIST:
+            raise TypeError(f"concat over arrays got {dt}")
+        return dt
+
+    def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
+        dt = self.dtype(schema)
+        return ops.array_concat(
+            [e.eval(batch, schema)
+             for e in _typed_operands(self.exprs, dt, schema)])
+
+    def __str__(self):
+        return f"concat({', '.join(str(e) for e in self.exprs)})"
+
+
+class Flatten(Expression):
+    """flatten(a) for a : array<array<T>>: the row's inner arrays in order
+    as one array<T>; NULL when the row or any inner array of it is
+    (GpuFlatten analogue)."""
+
+    def __init__(self, child: Expression):
+        self.child = child
+
+    @property
+    def children(self):
+        return (self.child,)
+
+    def dtype(self, schema: Schema) -> DType:
+        cdt = self.child.dtype(schema)
+        if cdt.id is not TypeId.LIST or \
+                cdt.children[0].id is not TypeId.LIST:
+            raise TypeError(f"flatten needs an array of arrays, got {cdt}")
+        return cdt.children[0]
+
+    def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
+        self.dtype(schema)
+        return ops.array_flatten(self.child.eval(batch, schema))
+
+    def __str__(self):
+        return f"flatten({self.child})"
+
+
+def _sequence_operand(what: str, v) -> Expression:
+    if isinstance(v, bool) or not isinstance(v, (int, Expression)):
+        raise TypeError(f"sequence: {what} must be an int or an integer "
+                        f"expression, got {type(v).__name__}")
+    return _as_expr(v)
+
+
+class Sequence(Expression):
+    """sequence(start, stop[, step]): start, start + step, ... up to stop,
+    all INT32 or all INT64. Without a step it is 1 where start <= stop, else
+    -1. NULL when any operand is. start == stop gives [start] whatever the
+    step; otherwise a zero step, or one pointing away from stop, raises
+    ValueError (GpuSequence analogue; dates and timestamps are not
+    covered)."""
+
+    def __init__(self, start, stop, step=None):
+        self.start = _sequence_operand("start", start)
+        self.stop = _sequence_operand("stop", stop)
+        self.step = None if step is None else _sequence_operand("step", step)
+
+    @property
+    def children(self):
+        return tuple(e for e in (self.start, self.stop, self.step)
+                     if e is not None)
+
+    def _operands(self, schema: Schema):
+        """The operands at their one type. A python int given next to an
+        INT64 operand was inferred as INT32 by its value alone, so it takes
+        the other operands' type; expressions are never cast."""
+        exprs = list(self.children)
+        typed = [e.dtype(schema) for e in exprs
+                 if not isinstance(e, Literal)]
+        if typed and all(t == typed[0] for t in typed) and \
+                typed[0].id in (TypeId.INT32, TypeId.INT64):
+            exprs = [Literal(e.value, typed[0])
+                     if isinstance(e, Literal) and
+                     (e.value is None or e.dtype(schema).is_integral)
+                     else e for e in exprs]
+        dt = _one_operand_type("sequence", exprs, schema)
+        if dt.id not in (TypeId.INT32, TypeId.INT64):
+            raise TypeError(f"sequence needs INT32 or INT64 operands, got "
+                            f"{dt}")
+        for e in exprs:
+            if isinstance(e, Literal) and e.value is not None and \
+                    dt.id is TypeId.INT32 and \
+                    not -(2 ** 31) <= e.value < 2 ** 31:
+                raise TypeError(f"sequence: {e.value} is outside INT32")
+        exprs = _typed_operands(exprs, dt, schema)
+        return dt, exprs[0], exprs[1], (exprs[2] if len(exprs) > 2 else None)
+
+    def dtype(self, schema: Schema) -> DType:
+        return DType.list_(self._operands(schema)[0])
+
+    def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
+        _, start, stop, step = self._operands(schema)
+        return ops.sequence(start.eval(batch, schema),
+                            stop.eval(batch, schema),
+                            None if step is None
+                            else step.eval(batch, schema))
+
+    def __str__(self):
+        return "sequence(" + ", ".join(str(e) for e in self.children) + ")"
+
+
+class ArrayJoin(Expression):
+    """array_join(a, delimiter[, null_replacement]) for a : array<string>:
+    the non-null elements joined by the delimiter; null elements are
+    skipped, or stand as the replacement when one is given. The delimiter
+    and the replacement are string literals. NULL when the array is
+    (GpuArrayJoin analogue)."""
+
+    def __init__(self, child: Expression, delimiter: str,
+                 null_replacement: Optional[str] = None):
+        for what, v in (("delimiter", delimiter),
+                        ("null replacement", null_replacement)):
+            if isinstance(v, Literal):
+                v = v.value
+            if not isinstance(v, str) and \
+                    not (v is None and what != "delimiter"):
+                raise TypeError(f"array_join: the {what} must be a string "
+                                f"literal, got {type(v).__name__}")
+        self.child = child
+        self.delimiter = delimiter.value if isinstance(delimiter, Literal) \
+            else delimiter
+        self.null_replacement = null_replacement.value \
+            if isinstance(null_replacement, Literal) else null_replacement
+
+    @property
+    def children(self):
+        return (self.child,)
+
+    def dtype(self, schema: Schema) -> DType:
+        cdt = self.child.dtype(schema)
+        if cdt.id is not TypeId.LIST or \
+                cdt.children[0].id is not TypeId.STRING:
+            raise TypeError(f"array_join needs an array of strings, got "
+                            f"{cdt}")
+        return STRING
+
+    def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
+        self.dtype(schema)
+        return ops.array_join(self.child.eval(batch, schema), self.delimiter,
+                              self.null_replacement)
+
+    def __str__(self):
+        r = "" if self.null_replacement is None \
+            else f", {self.null_replacement!r}"
+        return f"array_join({self.child}, {self.delimiter!r}{r})"
+
+
 _lambda_ids = itertools.count()
 
 
@@ -1210,7 +1475,7 @@ class LambdaFunction(Expression):
     """`x -> body` or `(x, i) -> body`; typed and evaluated against the
     element schema of the higher-order function that owns it."""
 
-    def __init__(self, args: Sequence[LambdaVariable], body: Expression):
+    def __init__(self, args: _Seq[LambdaVariable], body: Expression):
         self.args = tuple(args)
         self.body = body
 
@@ -1467,6 +1732,23 @@ def slice_(a, start, length) -> ArraySlice:
 
 def array_repeat(e, count) -> ArrayRepeat:
     return ArrayRepeat(e, count)
+
+
+def array(*exprs) -> CreateArray:
+    return CreateArray(*exprs)
+
+
+def flatten(a) -> Flatten:
+    return _as_expr(a).flatten()
+
+
+def sequence(start, stop, step=None) -> Sequence:
+    return Sequence(start, stop, step)
+
+
+def array_join(a, delimiter: str,
+               null_replacement: Optional[str] = None) -> ArrayJoin:
+    return _as_expr(a).array_join(delimiter, null_replacement)
 
 
 class HostStringFn(Expression):

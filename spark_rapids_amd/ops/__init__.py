@@ -139,6 +139,45 @@ def array_repeat(elem: Column, count: Column) -> Column:
     return backend_for(elem, count).array_repeat(elem, count)
 
 
+def create_array(cols: Sequence[Column]) -> Column:
+    """array(c1, ..., ck): row i is [c1[i], ..., ck[i]]; the row is never
+    NULL, an element is null where its operand is. The operands have one
+    type and one size (GpuCreateArray analogue)."""
+    return backend_for(*cols).create_array(list(cols))
+
+
+def array_concat(cols: Sequence[Column]) -> Column:
+    """concat(a1, ..., ak) over LIST columns of one type: the rows'
+    elements in operand order, null elements kept; NULL when any operand
+    row is (GpuConcat analogue)."""
+    return backend_for(*cols).array_concat(list(cols))
+
+
+def array_flatten(col: Column) -> Column:
+    """flatten(LIST<LIST<T>>): the row's inner arrays concatenated; NULL
+    when the row or any inner array of it is (GpuFlatten analogue)."""
+    return backend_for(col).array_flatten(col)
+
+
+def sequence(start: Column, stop: Column,
+             step: Optional[Column] = None) -> Column:
+    """sequence(start, stop[, step]) over INT32 or INT64 columns of one
+    type; step None is 1 where start <= stop, else -1. NULL when any
+    operand is; a zero step or one pointing away from stop (with start !=
+    stop) raises ValueError for the first such row; a result over
+    2**31 - 1 elements raises OverflowError (GpuSequence analogue)."""
+    cols = [c for c in (start, stop, step) if c is not None]
+    return backend_for(*cols).sequence(start, stop, step)
+
+
+def array_join(col: Column, delimiter: str,
+               null_replacement: Optional[str] = None) -> Column:
+    """array_join(LIST<STRING>, delimiter[, replacement]): the non-null
+    elements joined by the delimiter, null ones skipped or replaced; NULL
+    when the array is (GpuArrayJoin analogue)."""
+    return backend_for(col).array_join(col, delimiter, null_replacement)
+
+
 def list_span(col: Column) -> Tuple[int, int]:
     """(offsets[0], offsets[n] - offsets[0]) of a LIST column: where its
     elements start in the child and how many there are. The one host read

@@ -912,6 +912,123 @@ def array_repeat(elem: Column, count: Column) -> Column:
     return Column.from_pylist(out, DType.list_(elem.dtype))
 
 
+def _same_type_operands(fn: str, cols, want_list: bool) -> None:
+    if not cols:
+        raise ValueError(f"{fn} needs at least one operand")
+    dt = cols[0].dtype
+    if want_list and dt.id is not TypeId.LIST:
+        raise TypeError(f"{fn} needs array operands, got {dt}")
+    for c in cols[1:]:
+        if c.dtype != dt:
+            raise TypeError(f"{fn} needs operands of one type, got {dt} "
+                            f"and {c.dtype}")
+        if c.size != cols[0].size:
+            raise ValueError(f"{fn}: operands of {cols[0].size} and "
+                             f"{c.size} rows")
+
+
+def create_array(cols) -> Column:
+    """Row i is [c1[i], ..., ck[i]]; never NULL."""
+    _same_type_operands("array", cols, False)
+    if cols[0].size * len(cols) > 2 ** 31 - 1:
+        raise OverflowError("array result exceeds int32 offsets")
+    rows = [list(r) for r in zip(*(c.to_pylist() for c in cols))]
+    return Column.from_pylist(rows, DType.list_(cols[0].dtype))
+
+
+def array_concat(cols) -> Column:
+    """The rows' elements in operand order; NULL when any operand row is."""
+    _same_type_operands("concat", cols, True)
+    out = []
+    for parts in zip(*(c.to_pylist() for c in cols)):
+        if any(p is None for p in parts):
+            out.append(None)
+        else:
+            out.append([e for p in parts for e in p])
+    if sum(len(r) for r in out if r is not None) > 2 ** 31 - 1:
+        raise OverflowError("concat result exceeds int32 offsets")
+    return Column.from_pylist(out, cols[0].dtype)
+
+
+def array_flatten(col: Column) -> Column:
+    """The row's inner arrays concatenated; NULL when the row or any inner
+    array of it is."""
+    if col.dtype.id is not TypeId.LIST or \
+            col.dtype.children[0].id is not TypeId.LIST:
+        raise TypeError(f"flatten needs an array of arrays, got {col.dtype}")
+    out = []
+    for v in col.to_pylist():
+        if v is None or any(p is None for p in v):
+            out.append(None)
+        else:
+            out.append([e for p in v for e in p])
+    return Column.from_pylist(out, col.dtype.children[0])
+
+
+SEQUENCE_ERROR = "Illegal sequence boundaries: {} to {} by {}"
+SEQUENCE_OVERFLOW = "sequence result exceeds int32 offsets"
+
+
+def _sequence_operands(start: Column, stop: Column, step) -> None:
+    dt = start.dtype
+    if dt.id not in (TypeId.INT32, TypeId.INT64):
+        raise TypeError(f"sequence needs INT32 or INT64 operands, got {dt}")
+    for what, c in (("stop", stop), ("step", step)):
+        if c is None:
+            continue
+        if c.dtype != dt:
+            raise TypeError(f"sequence: start is {dt} and {what} is "
+                            f"{c.dtype}")
+        if c.size != start.size:
+            raise ValueError(f"sequence: {start.size} rows and {c.size} "
+                             f"{what} values")
+
+
+def sequence(start: Column, stop: Column, step=None) -> Column:
+    """start, start + step, ... up to stop; python ints, so no overflow."""
+    _sequence_operands(start, stop, step)
+    n = start.size
+    steps = step.to_pylist() if step is not None else [0] * n
+    rows = []
+    total = 0
+    for a, b, s in zip(start.to_pylist(), stop.to_pylist(), steps):
+        if a is None or b is None or s is None:
+            rows.append(None)
+            continue
+        if step is None:
+            s = 1 if a <= b else -1
+        if a == b:
+            count = 1
+        elif s == 0 or (b > a) != (s > 0):
+            raise ValueError(SEQUENCE_ERROR.format(a, b, s))
+        else:
+            count = 1 + abs(b - a) // abs(s)
+        total += count
+        rows.append((a, s, count))
+    if total > 2 ** 31 - 1:
+        raise OverflowError(SEQUENCE_OVERFLOW)
+    out = [None if r is None else [r[0] + i * r[1] for i in range(r[2])]
+           for r in rows]
+    return Column.from_pylist(out, DType.list_(start.dtype))
+
+
+def array_join(col: Column, delimiter: str, null_replacement=None) -> Column:
+    """Non-null elements joined by the delimiter; null ones are skipped, or
+    replaced when a replacement is given."""
+    if col.dtype.id is not TypeId.LIST or \
+            col.dtype.children[0].id is not TypeId.STRING:
+        raise TypeError(f"array_join needs an array of strings, got "
+                        f"{col.dtype}")
+    out = []
+    for v in col.to_pylist():
+        if v is None:
+            out.append(None)
+            continue
+        parts = [null_replacement if e is None else e for e in v]
+        out.append(delimiter.join(p for p in parts if p is not None))
+    return Column.from_pylist(out, DType.string())
+
+
 def list_span(col: Column):
     """(first offset, child rows covered)."""
     n = col.size

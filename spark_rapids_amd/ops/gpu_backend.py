@@ -18,7 +18,9 @@ import torch
 from ..column import (Column, ColumnBatch, DictColumn, mask_nbytes,
                       torch_dtype)
 from ..types import DType, TypeId
-from .cpu_backend import SLICE_LENGTH_ERROR, SLICE_START_ERROR
+from .cpu_backend import (SEQUENCE_ERROR, SEQUENCE_OVERFLOW,
+                          SLICE_LENGTH_ERROR, SLICE_START_ERROR,
+                          _same_type_operands, _sequence_operands)
 
 import importlib
 
@@ -1534,6 +1536,260 @@ def array_repeat(elem: Column, count: Column) -> Column:
     v = count.validity.clone() if count.validity is not None else None
     return Column(dtype, n, torch.zeros(0, dtype=torch.uint8, device="cuda"),
                   v, new_offs, count._null_count, child)
+
+
+# builders: array(), concat, flatten, sequence, array_join
+
+_LIST_MAX_OPERANDS = 8  # HIPDF_LIST_MAX_OPERANDS: operands of one launch
+_NO_DATA = dict(dtype=torch.uint8, device="cuda")
+
+
+def _list_operands(ptrs, valids) -> torch.Tensor:
+    """HipdfListOperands in host memory for up to 8 operands; the entry
+    point reads it during the call and hands it to the kernel by value."""
+    pad = [0] * (_LIST_MAX_OPERANDS - len(ptrs))
+    return torch.frombuffer(
+        bytearray(struct.pack("<16q", *ptrs, *pad, *valids, *pad)),
+        dtype=torch.uint8)
+
+
+def _no_nested(fn: str, et: DType) -> None:
+    if et.is_nested:
+        raise NotImplementedError(f"{fn} over nested elements runs on the "
+                                  "CPU")
+
+
+def _concat_cols(cols) -> Column:
+    if len(cols) == 1:
+        return cols[0]
+    return concat_batches([ColumnBatch([c], c.size) for c in cols]).columns[0]
+
+
+def create_array(cols) -> Column:
+    """array(c1, ..., ck). Fixed-width operands (<= 64 bit) go through
+    list_interleave, 8 per launch; strings and decimal128 through one
+    gather over the concatenated operands (list_interleave_map)."""
+    _same_type_operands("array", cols, False)
+    k, n, et = len(cols), cols[0].size, cols[0].dtype
+    _no_nested("array", et)
+    dtype = DType.list_(et)
+    s = _stream()
+    if n == 0:
+        return Column.from_pylist([], dtype).cuda()
+    total = n * k
+    if total > 2 ** 31 - 1:
+        raise OverflowError("array result exceeds int32 offsets")
+    new_offs = torch.empty(n + 1, dtype=torch.int32, device="cuda")
+    if et.id in (TypeId.STRING, TypeId.DECIMAL128):
+        idx = torch.empty(total, dtype=torch.int32, device="cuda")
+        ext.list_interleave_map(k, idx.data_ptr(), new_offs.data_ptr(), n, s)
+        child = _gather_col(_concat_cols(cols), idx, total,
+                            maybe_negative=False)
+    else:
+        out = _alloc(total, et)
+        shared = k > _LIST_MAX_OPERANDS  # launches share validity words
+        ov = None
+        if any(c.validity is not None for c in cols):
+            ov = torch.zeros(mask_nbytes(total), **_NO_DATA) if shared \
+                else _alloc_mask(total)
+        for j0 in range(0, k, _LIST_MAX_OPERANDS):
+            part = cols[j0:j0 + _LIST_MAX_OPERANDS]
+            ops_ = _list_operands([c.data.data_ptr() for c in part],
+                                  [_ptr(c.validity) for c in part])
+            ext.list_interleave(et.itemsize, ops_.data_ptr(), k, j0,
+                                len(part), int(shared), out.data_ptr(),
+                                _ptr(ov), new_offs.data_ptr() if j0 == 0
+                                else 0, n, s)
+        child = Column(et, total, out, ov,
+                       null_count=None if ov is not None else 0)
+    return Column(dtype, n, torch.zeros(0, **_NO_DATA), None, new_offs, 0,
+                  child)
+
+
+def array_concat(cols) -> Column:
+    """concat(a1, ..., ak): list_concat_lens sums the rows' lengths (8
+    operands per launch), they scan into the offsets, list_concat_map
+    writes one gather map over the concatenated children."""
+    _same_type_operands("concat", cols, True)
+    k, n, dtype = len(cols), cols[0].size, cols[0].dtype
+    _no_nested("concat", dtype.children[0])
+    s = _stream()
+    if n == 0:
+        return Column.from_pylist([], dtype).cuda()
+    bases = [0]
+    for c in cols:
+        bases.append(bases[-1] + c.child.size)
+    if bases[-1] > 2 ** 31 - 1:
+        raise OverflowError("concat operands exceed an int32 gather map")
+    out_len = torch.empty(n + 1, dtype=torch.int64, device="cuda")
+    ov = _alloc_mask(n)
+    launches = []  # (operand block, operand count, base rows, prefix)
+    for j0 in range(0, k, _LIST_MAX_OPERANDS):
+        part = cols[j0:j0 + _LIST_MAX_OPERANDS]
+        ops_ = _list_operands([c.offsets.data_ptr() for c in part],
+                              [_ptr(c.validity) for c in part])
+        prefix = torch.empty(n, dtype=torch.int32, device="cuda") \
+            if j0 else None
+        ext.list_concat_lens(ops_.data_ptr(), len(part), int(j0 == 0),
+                             int(j0 + _LIST_MAX_OPERANDS >= k),
+                             out_len.data_ptr(), _ptr(prefix), ov.data_ptr(),
+                             n, s)
+        launches.append((ops_, len(part), bases[j0:j0 + len(part)], prefix))
+    scanned, total = _exclusive_scan_i64(out_len)
+    if total > 2 ** 31 - 1:
+        raise OverflowError("concat result exceeds int32 offsets")
+    new_offs = torch.empty(n + 1, dtype=torch.int32, device="cuda")
+    ext.narrow_i64_i32(scanned.data_ptr(), new_offs.data_ptr(), n + 1, s)
+    if total:
+        idx = torch.empty(total, dtype=torch.int32, device="cuda")
+        for ops_, kk, base, prefix in launches:
+            cbase = torch.tensor(base, dtype=torch.int64)
+            ext.list_concat_map(ops_.data_ptr(), cbase.data_ptr(), kk,
+                                new_offs.data_ptr(), _ptr(prefix), n,
+                                idx.data_ptr(), total, s)
+        child = _gather_col(_concat_cols([c.child for c in cols]), idx, total,
+                            maybe_negative=False)
+    else:
+        child = _empty_col(dtype.children[0])
+    return Column(dtype, n, torch.zeros(0, **_NO_DATA), ov, new_offs, None,
+                  child)
+
+
+def _rows_view(c: Column, first: int, end: int) -> Column:
+    """Rows [first, end) of a flat column: a view where the buffers allow
+    one (validity words must start on a word), else a gather."""
+    m = end - first
+    if m == 0:
+        return _empty_col(c.dtype)
+    if first == 0 and end == c.size:
+        return c
+    plain = not isinstance(c, DictColumn) and c.dtype.id is not TypeId.STRUCT
+    if plain and (c.validity is None or first % 64 == 0):
+        v = None if c.validity is None else c.validity[first // 8:]
+        nc = None if v is not None else 0
+        if c.dtype.id is not TypeId.STRING:
+            w = 2 if c.dtype.id is TypeId.DECIMAL128 else 1
+            return Column(c.dtype, m, c.data[first * w:end * w], v,
+                          null_count=nc)
+        if first == 0:  # string offsets stay absolute, so only a prefix
+            return Column(c.dtype, m, c.data, v, c.offsets[:m + 1], nc)
+    idx = torch.empty(m, dtype=torch.int32, device="cuda")
+    ext.iota_i32(idx.data_ptr(), m, _stream())
+    if first:
+        idx = binary_op_scalar(
+            "add", Column(DType.int32(), m, idx, None, null_count=0), first,
+            DType.int32()).data
+    return _gather_col(c, idx, m, maybe_negative=False)
+
+
+def array_flatten(col: Column) -> Column:
+    """flatten(LIST<LIST<T>>): list_flatten composes the two offset arrays
+    and folds the inner validity into the rows'; the innermost child is
+    the result's child, cut to the rows' span."""
+    if col.dtype.id is not TypeId.LIST or \
+            col.dtype.children[0].id is not TypeId.LIST:
+        raise TypeError(f"flatten needs an array of arrays, got {col.dtype}")
+    dtype = col.dtype.children[0]
+    _no_nested("flatten", dtype.children[0])
+    n = col.size
+    if n == 0:
+        return Column.from_pylist([], dtype).cuda()
+    inner = col.child
+    new_offs = torch.empty(n + 1, dtype=torch.int32, device="cuda")
+    ov = _alloc_mask(n)
+    span = torch.empty(2, dtype=torch.int64, device="cuda")
+    # 8 lanes per row: the inner arrays of a row are few
+    ext.list_flatten(col.offsets.data_ptr(), _ptr(col.validity),
+                     inner.offsets.data_ptr(), _ptr(inner.validity), 8,
+                     new_offs.data_ptr(), ov.data_ptr(), span.data_ptr(), n,
+                     _stream())
+    first, end = (int(x) for x in span.tolist())  # the one host read
+    return Column(dtype, n, torch.zeros(0, **_NO_DATA), ov, new_offs, None,
+                  _rows_view(inner.child, first, end))
+
+
+def sequence(start: Column, stop: Column,
+             step: Optional[Column] = None) -> Column:
+    """sequence(start, stop[, step]): sequence_ranges gives the lengths,
+    the validity and the first illegal row with its values, which comes
+    back with the scan total; sequence_fill writes the elements."""
+    _sequence_operands(start, stop, step)
+    n = start.size
+    s = _stream()
+    dtype = DType.list_(start.dtype)
+    if n == 0:
+        return Column.from_pylist([], dtype).cuda()
+    t = _ht(start.dtype)
+    out_len = torch.empty(n + 1, dtype=torch.int64, device="cuda")
+    ov = _alloc_mask(n)
+    err = torch.tensor([2 ** 63 - 1, 0, 0, 0], dtype=torch.int64).cuda()
+    step_ptr = step.data.data_ptr() if step is not None else 0
+    ext.sequence_ranges(t, start.data.data_ptr(), _ptr(start.validity),
+                        stop.data.data_ptr(), _ptr(stop.validity), step_ptr,
+                        _ptr(step.validity) if step is not None else 0,
+                        out_len.data_ptr(), ov.data_ptr(), err.data_ptr(), n,
+                        s)
+    scanned, total, (bad, a, b, st) = _exclusive_scan_i64(out_len, err)
+    if bad < n:
+        raise ValueError(SEQUENCE_ERROR.format(a, b, st))
+    if total > 2 ** 31 - 1:
+        raise OverflowError(SEQUENCE_OVERFLOW)
+    new_offs = torch.empty(n + 1, dtype=torch.int32, device="cuda")
+    ext.narrow_i64_i32(scanned.data_ptr(), new_offs.data_ptr(), n + 1, s)
+    out = _alloc(total, start.dtype)
+    ext.sequence_fill(t, new_offs.data_ptr(), start.data.data_ptr(),
+                      stop.data.data_ptr(), step_ptr, n, out.data_ptr(),
+                      total, s)
+    child = Column(start.dtype, total, out, None, null_count=0)
+    return Column(dtype, n, torch.zeros(0, **_NO_DATA), ov, new_offs, None,
+                  child)
+
+
+def array_join(col: Column, delimiter: str,
+               null_replacement: Optional[str] = None) -> Column:
+    """array_join: array_join_sizes gives every element's bytes with its
+    delimiter, their scan places the elements, array_join_rows turns it
+    into row lengths, whose scan gives the string offsets, and
+    array_join_write copies element-parallel."""
+    if col.dtype.id is not TypeId.LIST or \
+            col.dtype.children[0].id is not TypeId.STRING:
+        raise TypeError(f"array_join needs an array of strings, got "
+                        f"{col.dtype}")
+    n = col.size
+    s = _stream()
+    if n == 0:
+        return _empty_col(DType.string())
+    v = col.validity.clone() if col.validity is not None else None
+    _, total = list_span(col)
+    if total == 0:  # every row is empty or null
+        return Column(DType.string(), n, torch.zeros(0, **_NO_DATA), v,
+                      torch.zeros(n + 1, dtype=torch.int32, device="cuda"),
+                      col._null_count)
+    d = _pattern_tensor(delimiter)
+    has_repl = null_replacement is not None
+    r = _pattern_tensor(null_replacement if has_repl else "")
+    dlen, rlen = d.numel(), (r.numel() if has_repl else -1)
+    ch = col.child
+    contrib = torch.empty(total + 1, dtype=torch.int64, device="cuda")
+    ext.array_join_sizes(col.offsets.data_ptr(), _ptr(col.validity),
+                         ch.offsets.data_ptr(), _ptr(ch.validity), dlen, rlen,
+                         n, contrib.data_ptr(), total, s)
+    placed, _ = _exclusive_scan_i64(contrib)
+    out_len = torch.empty(n + 1, dtype=torch.int64, device="cuda")
+    ext.array_join_rows(col.offsets.data_ptr(), placed.data_ptr(), dlen, n,
+                        out_len.data_ptr(), s)
+    out_off, nbytes = _exclusive_scan_i64(out_len)
+    if nbytes > 2 ** 31 - 1:
+        raise OverflowError("array_join result exceeds int32 offsets")
+    out = torch.empty(max(nbytes, 1), **_NO_DATA)[:nbytes]
+    ext.array_join_write(col.offsets.data_ptr(), _ptr(col.validity),
+                         ch.offsets.data_ptr(), ch.data.data_ptr(),
+                         _ptr(ch.validity), d.data_ptr(), dlen, r.data_ptr(),
+                         rlen, placed.data_ptr(), out_off.data_ptr(), n,
+                         out.data_ptr(), total if nbytes else 0, s)
+    offs = torch.empty(n + 1, dtype=torch.int32, device="cuda")
+    ext.narrow_i64_i32(out_off.data_ptr(), offs.data_ptr(), n + 1, s)
+    return Column(DType.string(), n, out, v, offs, col._null_count)
 
 
 def _array_extreme(col: Column, is_max: bool) -> Column:

@@ -74,6 +74,9 @@ _ARRAY_SET_OPS = ("ArrayUnion", "ArrayIntersect", "ArrayExcept",
 _ARRAY_SEARCH_FNS = {"ArrayPosition": "array_position",
                      "ArrayRemove": "array_remove", "ArraySlice": "slice",
                      "ArrayRepeat": "array_repeat"}
+_ARRAY_BUILD_FNS = {"CreateArray": "array", "ArrayConcat": "concat",
+                    "Flatten": "flatten", "Sequence": "sequence",
+                    "ArrayJoin": "array_join"}
 _ARRAY_LAMBDAS = ("ArrayTransform", "ArrayFilter", "ArrayExists",
                   "ArrayForAll")
 
@@ -118,6 +121,14 @@ class Tagger:
                     out.append(f"cast {src} -> string not on GPU yet")
             if not self.conf.expr_enabled("Cast"):
                 out.append("expression Cast disabled by conf")
+        elif isinstance(e, BinaryExpr) and \
+                e._array_concat(schema) is not None:
+            # concat over arrays: the whole chain is one ArrayConcat
+            arrays = e._array_concat(schema)
+            self._tag_array_build(arrays, schema, out)
+            for c in arrays.children:
+                self._tag_expr(c, schema, out)
+            return
         elif isinstance(e, BinaryExpr):
             lt, rt = e.left.dtype(schema), e.right.dtype(schema)
             if e.op in ("mul", "div") and _decimal_exact(lt, rt):
@@ -194,6 +205,8 @@ class Tagger:
                     out.append(f"{fn} over {et} elements on CPU")
         elif type(e).__name__ in _ARRAY_SEARCH_FNS:
             self._tag_array_search(e, schema, out)
+        elif type(e).__name__ in _ARRAY_BUILD_FNS:
+            self._tag_array_build(e, schema, out)
         elif type(e).__name__ == "LambdaVariable":
             pass
         elif type(e).__name__ in _ARRAY_LAMBDAS:
@@ -259,6 +272,20 @@ class Tagger:
                 out.append(f"{fn} over decimal128 elements on CPU")
             elif not (et.is_fixed_width or et.id is TypeId.STRING):
                 out.append(f"{fn} over {et} elements on CPU")
+
+    def _tag_array_build(self, e, schema, out: List[str]):
+        """array / concat / flatten only move elements (the interleave
+        kernel or the gather), so every element type but a nested one runs
+        on the GPU, decimal128 included. sequence and array_join have one
+        element type each, which dtype() checks."""
+        name = type(e).__name__
+        fn = _ARRAY_BUILD_FNS[name]
+        if not self.conf.expr_enabled(name):
+            out.append(f"expression {name} disabled by conf")
+        rt = e.dtype(schema)
+        if name in ("CreateArray", "ArrayConcat", "Flatten") and \
+                rt.children[0].is_nested:
+            out.append(f"{fn} over nested elements on CPU")
 
     def _tag_array_lambda(self, e, schema, out: List[str]):
         """transform / filter / exists / forall: the body runs as ordinary

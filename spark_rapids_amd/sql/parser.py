@@ -919,6 +919,24 @@ class Parser:
                 raise ValueError("slice takes three arguments")
             return ArraySlice(args[0], self._int_operand(args[1]),
                               self._int_operand(args[2]))
+        if name in ("array", "flatten", "sequence", "array_join"):
+            from ..expr import expressions as _ex
+
+            if name == "array":
+                if not args:
+                    raise ValueError("array takes at least one argument")
+                return _ex.CreateArray(*args)
+            if name == "flatten":
+                if len(args) != 1:
+                    raise ValueError("flatten takes one argument")
+                return _ex.Flatten(args[0])
+            if name == "sequence":
+                if len(args) not in (2, 3):
+                    raise ValueError("sequence takes two or three arguments")
+                return _ex.Sequence(*[self._int_operand(a) for a in args])
+            if len(args) not in (2, 3):
+                raise ValueError("array_join takes two or three arguments")
+            return _ex.ArrayJoin(args[0], *args[1:])
         if name in ("map_keys", "map_values", "map_entries"):
             from ..expr.expressions import MapView
 

@@ -238,7 +238,21 @@ _EXPR_ROWS = [
     ("ArrayRepeat", "array_repeat(e, n)", "GPU",
      "lengths scan into offsets, element-to-row map as the gather map; "
      "nested elements CPU"),
-    ("CreateArray", "from_pylist lists", "CPU", "construction host-side"),
+    ("CreateArray", "array(e1, ..., ek)", "GPU",
+     "list_interleave, 8 operands per launch; strings and decimal128 "
+     "through one gather; nested operands CPU"),
+    ("ArrayConcat", "concat(a1, ..., ak) over arrays", "GPU",
+     "row lengths scan into offsets, one gather map over the operands' "
+     "children; nested elements CPU"),
+    ("Flatten", "flatten(a)", "GPU",
+     "offsets composed on device, innermost child reused as a view; "
+     "nested elements CPU"),
+    ("Sequence", "sequence(start, stop[, step])", "GPU",
+     "INT32/INT64; illegal boundaries raise with the first bad row's "
+     "values; dates and timestamps not covered"),
+    ("ArrayJoin", "array_join(a, d[, r])", "GPU",
+     "element-parallel sizes and write around two device scans; literal "
+     "delimiter and replacement"),
     # misc
     ("Rand", "SampleHash deterministic draw", "GPU", "sample() lowering"),
     ("SparkPartitionID", "rank literal", "GPU", ""),
