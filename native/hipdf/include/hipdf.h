@@ -879,11 +879,19 @@ typedef struct {
   int64_t num_values;
   int32_t group;       /* hand-over unit (file index), 0 .. n_groups-1 */
   int32_t max_def;
+  /* device: the destination column's LSB-first validity mask, zeroed before
+   * the submit, or NULL. NULL: the chunk must be all valid (the rule and the
+   * error codes of hipdf_pq_plain_pieces). Not NULL: max_def must be 1, the
+   * chunk may hold nulls, null rows of dst are written as zero and bit
+   * valid_bit0 + i of the mask is set when row i of the chunk is valid. */
+  void* valid;
+  int64_t valid_bit0;  /* bit of the chunk's first row; any offset */
 } HipdfScanChunk;
-HIPDF_STATIC_ASSERT(sizeof(HipdfScanChunk) == 48, "packed as <qqiiqqii");
+HIPDF_STATIC_ASSERT(sizeof(HipdfScanChunk) == 64, "packed as <qqiiqqiiqq");
 
 typedef struct HipdfScanReader HipdfScanReader;
-/* at most 8 worker threads, each with a scratch buffer of piece_bytes;
+/* at most 8 worker threads, each with a scratch buffer of piece_bytes (and
+ * the mask words and tile counts of a nullable slice of that many bytes);
  * n_streams <= n_threads copy streams. NULL on failure. */
 HipdfScanReader* hipdf_scan_open(int n_threads, int n_streams,
                                  int64_t piece_bytes);
@@ -891,7 +899,10 @@ HipdfScanReader* hipdf_scan_open(int n_threads, int n_streams,
  * them group-major. Every dst buffer must be allocated before the call (see
  * the memory rule in scan_reader.hip); an event recorded on `consumer` gates
  * the first write. Returns a ticket (> 0), or a negative code and nothing
- * queued: a hipdf_pq_plain_pieces code when a chunk is not eligible. */
+ * queued: a hipdf_pq_plain_pieces code when a chunk is not eligible. The
+ * definition levels of a chunk with a validity mask are decoded later, on the
+ * worker threads; a page whose levels are malformed or disagree with its
+ * value bytes fails the submit, which hipdf_scan_wait_group reports. */
 int64_t hipdf_scan_submit(HipdfScanReader* r, const HipdfScanChunk* chunks,
                           int64_t n_chunks, int n_groups,
                           hipStream_t consumer);

@@ -161,15 +161,17 @@ inline bool rle_all_valid(const uint8_t* lv, int64_t nb, int64_t n,
   return true;
 }
 
-// One entry per data page: out[3k] = offset of the page's values from the
-// start of the chunk, out[3k+1] = their byte length, out[3k+2] = number of
-// values. Returns the number of pages or a negative kErr* code.
-inline int64_t walk(const uint8_t* chunk, int64_t nbytes, int64_t num_values,
-                    int max_def, int phys_width, int64_t* out,
-                    int64_t max_out) {
+// The walk behind walk() and walk_levels(). with_levels = false: three
+// entries per page and every page all-valid. with_levels = true: five entries
+// per page (kLevelStride), pages with nulls accepted for max_def <= 1.
+inline int64_t walk_impl(const uint8_t* chunk, int64_t nbytes,
+                         int64_t num_values, int max_def, int phys_width,
+                         int64_t* out, int64_t max_out, bool with_levels) {
+  const int stride = with_levels ? 5 : 3;
   if (phys_width != 4 && phys_width != 8) return kErrWidth;
   if (nbytes < 0 || num_values < 0 || max_def < 0 || max_def > 127)
     return kErrMalformed;
+  if (with_levels && max_def > 1) return kErrNulls;
   Cursor c{chunk, 0, nbytes, true};
   int64_t decoded = 0, npages = 0;
   while (decoded < num_values && c.pos < nbytes) {
@@ -236,6 +238,7 @@ inline int64_t walk(const uint8_t* chunk, int64_t nbytes, int64_t num_values,
     if (csize != usize) return kErrCompressed;
     const int64_t page = c.pos;  // first payload byte
     int64_t vpos = 0;            // values start, relative to the payload
+    int64_t lpos = 0, llen = 0;  // def-level stream, relative to the payload
     if (!v2) {
       if (max_def > 0) {
         if (csize < 4) return kErrTruncated;
@@ -243,17 +246,23 @@ inline int64_t walk(const uint8_t* chunk, int64_t nbytes, int64_t num_values,
                        (uint32_t)chunk[page + 2] << 16 |
                        (uint32_t)chunk[page + 3] << 24;
         if ((int64_t)len > csize - 4) return kErrTruncated;
-        if (!rle_all_valid(chunk + page + 4, (int64_t)len, n, max_def))
+        if (!with_levels &&
+            !rle_all_valid(chunk + page + 4, (int64_t)len, n, max_def))
           return kErrNulls;
+        lpos = 4;
+        llen = (int64_t)len;
         vpos = 4 + (int64_t)len;
       }
     } else {
       if (rep_len != 0) return kErrNested;
       if (def_len < 0 || def_len > csize) return kErrMalformed;
       if (max_def > 0) {
-        if (nulls != 0) return kErrNulls;
-        if (!rle_all_valid(chunk + page, def_len, n, max_def))
-          return kErrNulls;
+        if (!with_levels) {
+          if (nulls != 0) return kErrNulls;
+          if (!rle_all_valid(chunk + page, def_len, n, max_def))
+            return kErrNulls;
+        }
+        llen = def_len;
       } else if (def_len != 0) {
         return kErrMalformed;
       }
@@ -263,12 +272,24 @@ inline int64_t walk(const uint8_t* chunk, int64_t nbytes, int64_t num_values,
       vpos = def_len;
     }
     // n * width cannot overflow: n is an i32
-    if (csize - vpos != n * (int64_t)phys_width) return kErrCompressed;
+    const int64_t vbytes = csize - vpos;
+    if (with_levels && max_def > 0) {
+      // the values are dense: how many there are is known only once the
+      // levels are decoded, and checked there
+      if (vbytes % phys_width != 0 || vbytes > n * (int64_t)phys_width)
+        return kErrCompressed;
+    } else if (vbytes != n * (int64_t)phys_width) {
+      return kErrCompressed;
+    }
     if (n > num_values - decoded) return kErrCount;
     if (npages >= max_out) return kErrCapacity;
-    out[3 * npages] = page + vpos;
-    out[3 * npages + 1] = n * (int64_t)phys_width;
-    out[3 * npages + 2] = n;
+    out[stride * npages] = page + vpos;
+    out[stride * npages + 1] = vbytes;
+    out[stride * npages + 2] = n;
+    if (with_levels) {
+      out[stride * npages + 3] = page + lpos;
+      out[stride * npages + 4] = llen;
+    }
     ++npages;
     decoded += n;
     c.pos = page + csize;
@@ -276,6 +297,16 @@ inline int64_t walk(const uint8_t* chunk, int64_t nbytes, int64_t num_values,
   if (decoded != num_values) return decoded < num_values ? kErrTruncated
                                                          : kErrCount;
   return npages;
+}
+
+// One entry per data page: out[3k] = offset of the page's values from the
+// start of the chunk, out[3k+1] = their byte length, out[3k+2] = number of
+// values. Returns the number of pages or a negative kErr* code.
+inline int64_t walk(const uint8_t* chunk, int64_t nbytes, int64_t num_values,
+                    int max_def, int phys_width, int64_t* out,
+                    int64_t max_out) {
+  return walk_impl(chunk, nbytes, num_values, max_def, phys_width, out,
+                   max_out, false);
 }
 
 }  // namespace pq_pieces

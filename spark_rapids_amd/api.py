@@ -583,7 +583,8 @@ class Session:
             reader = "GPU_DECODE" if (torch.cuda.is_available()
                                       and self.conf.sql_enabled) else "CPU"
         from .config import (BATCH_SIZE_BYTES, PARQUET_STREAM_SCAN,
-                             PARQUET_STREAM_SCAN_FILES)
+                             PARQUET_STREAM_SCAN_FILES,
+                             PARQUET_STREAM_SCAN_NULLS)
 
         src = ParquetTable(path, columns=columns, reader=reader,
                            prefetch_threads=self.conf.get(PARQUET_MT_THREADS),
@@ -591,7 +592,9 @@ class Session:
                            chunk_bytes=self.conf.get(BATCH_SIZE_BYTES),
                            stream_scan=self.conf.get(PARQUET_STREAM_SCAN),
                            stream_files=self.conf.get(
-                               PARQUET_STREAM_SCAN_FILES))
+                               PARQUET_STREAM_SCAN_FILES),
+                           stream_nulls=self.conf.get(
+                               PARQUET_STREAM_SCAN_NULLS))
         return DataFrame(self, L.Scan(src, src.schema, f"parquet:{path}"))
 
     def write_parquet(self, df: DataFrame, path: str,

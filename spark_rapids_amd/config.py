@@ -174,7 +174,8 @@ PARQUET_MT_THREADS = int_conf(
 PARQUET_STREAM_SCAN = bool_conf(
     "spark.rapids.sql.format.parquet.streamScan.enabled", True,
     "A multi-file GPU_DECODE scan whose selected column chunks are all "
-    "uncompressed PLAIN fixed-width pages without nulls is uploaded by the "
+    "uncompressed PLAIN fixed-width pages (with nulls: see "
+    "streamScan.nulls.enabled) is uploaded by the "
     "native in-order reader: the files arrive one after the other straight "
     "in their destination columns, the scan yields one batch per group of "
     "files while the later files are still being copied, and the upload "
@@ -185,6 +186,13 @@ PARQUET_STREAM_SCAN_FILES = int_conf(
     "the query's kernels run while later files are still being copied, and "
     "launch every per-batch kernel more often; measured on MI355X with 8 "
     "fact files, 4 was the best of 1, 2 and 4.")
+PARQUET_STREAM_SCAN_NULLS = bool_conf(
+    "spark.rapids.sql.format.parquet.streamScan.nulls.enabled", True,
+    "A stream scan also takes nullable columns (max definition level 1) "
+    "whose footers report nulls: the reader's worker threads decode each "
+    "page's definition levels into a validity bitmask on the host, and one "
+    "kernel per slice of a page places the dense values at their rows. "
+    "When false, a scan with such a column runs file by file as before.")
 BROADCAST_THRESHOLD = bytes_conf(
     "spark.rapids.sql.join.broadcastThreshold", 512 << 20,
     "Distributed joins all-gather (broadcast) the build side when its "

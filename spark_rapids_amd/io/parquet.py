@@ -224,12 +224,16 @@ class ParquetTable:
                  columns: Optional[List[str]] = None, reader: str = "CPU",
                  prefetch_threads: int = 4, replicated: bool = False,
                  chunk_bytes: int = 0, stream_scan: bool = False,
-                 stream_files: int = 4, stream_piece_bytes: int = 0):
+                 stream_files: int = 4, stream_piece_bytes: int = 0,
+                 stream_nulls: bool = False):
         # stream_scan: multi-file GPU_DECODE scans of PLAIN fixed-width
         # chunks go through the native in-order reader, one batch per
         # stream_files files (parquet_gpu.StreamScan); stream_piece_bytes
-        # overrides the reader's piece size (0 = its default)
+        # overrides the reader's piece size (0 = its default); stream_nulls
+        # lets that reader take columns whose footers report nulls (off:
+        # such a scan runs file by file)
         self.stream_scan = stream_scan
+        self.stream_nulls = stream_nulls
         self.stream_files = stream_files
         self.stream_piece_bytes = stream_piece_bytes
         # chunk_bytes > 0: a file whose decoded size exceeds the budget is
@@ -273,6 +277,7 @@ class ParquetTable:
         t.stream_scan = getattr(self, "stream_scan", False)
         t.stream_files = getattr(self, "stream_files", 4)
         t.stream_piece_bytes = getattr(self, "stream_piece_bytes", 0)
+        t.stream_nulls = getattr(self, "stream_nulls", False)
         return t
 
     def with_columns(self, names: List[str]) -> "ParquetTable":
@@ -389,7 +394,8 @@ class ParquetTable:
         """Submit this scan to the native in-order reader and return the
         running parquet_gpu.StreamScan, or None when the scan is not one
         for it (single file, another reader, conf off, host file cache on,
-        or a chunk that is not PLAIN fixed-width without nulls). The caller
+        a chunk that is not PLAIN fixed-width, or one with nulls while
+        stream_nulls is off). The caller
         consumes batches() or calls close()."""
         import torch
 

@@ -1027,10 +1027,11 @@ def _reader(threads: int, piece_bytes: int) -> int:
 def _stream_layout(table, files):
     """What a stream scan of `files` uploads, from the footers alone: per
     file its rows and one (column position, chunk offset, chunk bytes,
-    physical width, destination width, values, max def level) entry per
-    selected column chunk, or None when a chunk cannot be eligible (the page
-    headers are checked later, by the native walker). Cached per scan
-    shape, keyed on the files' mtimes like the footers."""
+    physical width, destination width, values, max def level, first row,
+    footer null count or None without statistics) entry per selected column
+    chunk, or None when a chunk cannot be eligible (the page headers are
+    checked later, by the native walker). Cached per scan shape, keyed on
+    the files' mtimes like the footers."""
     import os
 
     from ..column import torch_dtype
@@ -1086,10 +1087,15 @@ def _stream_layout(table, files):
                                                  and dt.is_decimal)) \
                             or cmd.num_values != rgmd.num_rows:
                         return None
+                    st = cmd.statistics if cmd.is_stats_set else None
+                    nulls = st.null_count \
+                        if st is not None and st.has_null_count else None
+                    if cmd.num_values == 0:
+                        nulls = 0  # pyarrow writes no statistics for it
                     chunks.append((ci, cmd.data_page_offset,
                                    cmd.total_compressed_size, pw, dw,
                                    cmd.num_values, sc.max_definition_level,
-                                   rows))
+                                   rows, nulls))
                 rows += rgmd.num_rows
             per_file.append((rows, chunks))
         if dtypes is None:
@@ -1128,6 +1134,7 @@ class StreamScan:
             return None
         dtypes, per_file = layout
         per_batch = max(1, int(getattr(table, "stream_files", 1)))
+        take_nulls = bool(getattr(table, "stream_nulls", False))
         tdts = [torch_dtype(d) for d in dtypes]
         batches = []
         descs = []
@@ -1138,25 +1145,56 @@ class StreamScan:
             rows = sum(r for r, _ in group)
             bufs = [torch.empty(max(rows, 1), dtype=t, device="cuda")[:rows]
                     for t in tdts]
+            # a column of the batch gets a validity mask when one of its
+            # chunks may hold nulls: max_def 1 and a footer null count that
+            # is not zero, or none. All-zero counts keep the strict
+            # all-valid walk.
+            masks = [None] * len(tdts)
+            null_counts = [0] * len(tdts)
+            for _, chunks in group:
+                for ch in chunks:
+                    ci, max_def, nulls = ch[0], ch[6], ch[8]
+                    if max_def == 0 or nulls == 0:
+                        continue
+                    if max_def != 1 or not take_nulls:
+                        return None
+                    if masks[ci] is None:
+                        # zeroed on the consumer stream, before the submit's
+                        # start event
+                        masks[ci] = torch.zeros(mask_nbytes(rows),
+                                                dtype=torch.uint8,
+                                                device="cuda")
+                    null_counts[ci] = None if nulls is None \
+                        or null_counts[ci] is None else null_counts[ci] + nulls
             base = 0
             for path, (frows, chunks) in zip(files[g:g + per_batch], group):
                 mm = _file_mmap(path)
                 keepalive.append(mm)
-                for ci, off, nb, pw, dw, nvals, max_def, row0 in chunks:
+                for ci, off, nb, pw, dw, nvals, max_def, row0, _ in chunks:
                     if off < 0 or off + nb > mm[3]:
                         return None
+                    m = masks[ci]
+                    if m is not None and max_def != 1:
+                        return None  # the files disagree on the schema
                     descs.append((mm[2] + off, nb, pw, dw,
                                   bufs[ci].data_ptr() + (base + row0) * dw,
-                                  nvals, len(batches), max_def))
-                    nbytes += nvals * pw
+                                  nvals, len(batches), max_def,
+                                  m.data_ptr() if m is not None else 0,
+                                  base + row0))
+                    # a chunk that may hold nulls uploads its dense values
+                    # and its levels (as a mask); nb counts those and the
+                    # few bytes of every page header
+                    nbytes += nvals * pw if m is None else nb
                 base += frows
             batches.append(ColumnBatch(
-                [Column(d, rows, b, None, null_count=0)
-                 for d, b in zip(dtypes, bufs)], rows))
+                [Column(d, rows, b, m, null_count=0 if m is None else nc)
+                 for d, b, m, nc in zip(dtypes, bufs, masks, null_counts)],
+                rows))
         table_np = np.array(descs, dtype=np.dtype(
             [("src", "<i8"), ("nbytes", "<i8"), ("pw", "<i4"), ("dw", "<i4"),
              ("dst", "<i8"), ("n", "<i8"), ("group", "<i4"),
-             ("max_def", "<i4")]))  # HipdfScanChunk
+             ("max_def", "<i4"), ("valid", "<i8"),
+             ("valid_bit0", "<i8")]))  # HipdfScanChunk
         reader = _reader(table.prefetch_threads,
                          getattr(table, "stream_piece_bytes", 0)
                          or STREAM_PIECE_BYTES)
