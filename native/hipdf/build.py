@@ -39,6 +39,7 @@ KERNELS = [
     "kernels/cast_str.hip",
     "kernels/datetime.hip",
     "kernels/lists.hip",
+    "kernels/digest.hip",
     "pool.hip",
     "scan_reader.hip",
 ]

@@ -409,6 +409,8 @@ PYBIND11_MODULE(hipdf, m) {
   BIND(xxhash64_col);
   BIND(xxhash64_str);
   BIND(pmod_part);
+  BIND(digest_hex);
+  BIND(crc32_str);
 
   // ---- group-by ----------------------------------------------------------
   BIND(gb_build);

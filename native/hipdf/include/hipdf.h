@@ -264,6 +264,20 @@ void hipdf_xxhash64_str(const void* offsets, const void* bytes,
 void hipdf_pmod_part(const void* h, int nparts, void* part, int64_t n,
                      hipStream_t stream);
 
+/* ---- digests (kernels/digest.hip) --------------------------------------- */
+/* md5 / sha1 / sha2 of each row's bytes as lowercase hex, thread per row.
+ * Row i's W digits go to out_bytes + i * W (W = 32, 40, 56, 64, 96, 128 by
+ * algo), so the result's offsets are i * W; a null row gets W '0' digits.
+ * out_bytes: n * W bytes, 16-byte aligned. */
+void hipdf_digest_hex(int algo, const void* offsets, const void* bytes,
+                      const void* av, void* out_bytes, int64_t n,
+                      hipStream_t stream);
+    /* algo: 0 md5, 1 sha1, 2 sha224, 3 sha256, 4 sha384, 5 sha512 */
+/* crc32 (zlib) of each row's bytes, unsigned, widened: out_i64 int64[n];
+ * a null row writes 0 */
+void hipdf_crc32_str(const void* offsets, const void* bytes, const void* av,
+                     void* out_i64, int64_t n, hipStream_t stream);
+
 /* ---- group-by (kernels/groupby.hip) ------------------------------------ */
 /* CAS hash build over a power-of-two slot table (cap slots, slot_row
  * int32[cap] initialized to -1); claimed_slots int32[n]; ngroups int32[1]

@@ -26,7 +26,8 @@ from .expr.expressions import (CaseWhen, ascii_, coalesce, col, concat_ws,
                                map_entries, transform, filter_, exists,
                                forall, array_position, array_remove, slice_,
                                array_repeat, array, flatten, sequence,
-                               array_join)
+                               array_join, md5, sha1, sha2, crc32, hash_,
+                               xxhash64)
 from .expr.windows import (dense_rank, lag, lead, nth_value, ntile,
                            rank, row_number, win_avg,
                            win_count, win_max, win_min, win_sum)

@@ -272,6 +272,16 @@ ALLOW_INCOMPAT = bool_conf(
 _PER_OP_PREFIX = "spark.rapids.sql.exec."
 _PER_EXPR_PREFIX = "spark.rapids.sql.expression."
 
+# Any spark.rapids.sql.expression.<ClassName> key switches that expression
+# off the GPU (RapidsConf.expr_enabled); the digest family's are documented.
+for _cls, _sql in (("Md5", "md5"), ("Sha1", "sha1 / sha"), ("Sha2", "sha2"),
+                   ("Crc32", "crc32"), ("Murmur3Hash", "hash"),
+                   ("XxHash64", "xxhash64")):
+    bool_conf(_PER_EXPR_PREFIX + _cls, True,
+              f"Run the {_cls} expression (SQL `{_sql}`) on the GPU; when "
+              "false the planner places it on the CPU.")
+del _cls, _sql
+
 
 class RapidsConf:
     """One immutable-ish view of configuration; sessions own one instance."""

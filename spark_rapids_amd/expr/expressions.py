@@ -1444,6 +1444,166 @@ class ArrayJoin(Expression):
         return f"array_join({self.child}, {self.delimiter!r}{r})"
 
 
+class _StringDigest(Expression):
+    """A function of one STRING operand's UTF-8 bytes (what Spark's implicit
+    string-to-binary cast hashes; there is no BINARY type). NULL where the
+    operand is. Any other operand type is a TypeError from dtype(), as
+    Spark rejects it at analysis time."""
+
+    fn = ""
+
+    def __init__(self, child):
+        self.child = _as_expr(child)
+
+    @property
+    def children(self):
+        return (self.child,)
+
+    def _check(self, schema: Schema):
+        cdt = self.child.dtype(schema)
+        if cdt.id is not TypeId.STRING:
+            raise TypeError(f"{self.fn} needs a string input, got {cdt}")
+
+    def dtype(self, schema: Schema) -> DType:
+        self._check(schema)
+        return STRING
+
+    def __str__(self):
+        return f"{self.fn}({self.child})"
+
+
+class Md5(_StringDigest):
+    """md5(s): 32 lowercase hex digits (GpuMd5 analogue)."""
+
+    fn = "md5"
+
+    def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
+        self._check(schema)
+        return ops.digest_hex(self.child.eval(batch, schema), "md5")
+
+
+class Sha1(_StringDigest):
+    """sha1(s) / sha(s): 40 lowercase hex digits (GpuSha1 analogue)."""
+
+    fn = "sha1"
+
+    def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
+        self._check(schema)
+        return ops.digest_hex(self.child.eval(batch, schema), "sha1")
+
+
+class Sha2(_StringDigest):
+    """sha2(s, bits): the SHA-2 digest of that many bits as lowercase hex.
+    bits is an int literal; 0 means 256; anything but 0, 224, 256, 384 and
+    512 gives NULL in every row, as in Spark (GpuSha2 analogue)."""
+
+    fn = "sha2"
+    _ALGO = {0: "sha256", 224: "sha224", 256: "sha256", 384: "sha384",
+             512: "sha512"}
+
+    def __init__(self, child, bits):
+        super().__init__(child)
+        if isinstance(bits, Literal):
+            bits = bits.value
+        if isinstance(bits, bool) or not isinstance(bits, int):
+            raise ValueError(f"sha2: the bit length must be an int literal, "
+                             f"got {bits}")
+        self.bits = bits
+
+    def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
+        self._check(schema)
+        algo = self._ALGO.get(self.bits)
+        if algo is None:
+            return Column.nulls(STRING, batch.num_rows, batch.device)
+        return ops.digest_hex(self.child.eval(batch, schema), algo)
+
+    def __str__(self):
+        return f"sha2({self.child}, {self.bits})"
+
+
+class Crc32(_StringDigest):
+    """crc32(s): the zlib CRC-32 as an unsigned value in a BIGINT (GpuCrc32
+    analogue)."""
+
+    fn = "crc32"
+
+    def dtype(self, schema: Schema) -> DType:
+        self._check(schema)
+        return INT64
+
+    def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
+        self._check(schema)
+        return ops.crc32(self.child.eval(batch, schema))
+
+
+# what murmur3_hash and xxhash64 hash in both backends today
+_ROW_HASH_TYPES = (TypeId.BOOL, TypeId.INT8, TypeId.INT16, TypeId.INT32,
+                   TypeId.DATE32, TypeId.INT64, TypeId.TIMESTAMP,
+                   TypeId.DECIMAL64, TypeId.FLOAT32, TypeId.FLOAT64,
+                   TypeId.STRING)
+
+
+class _RowHash(Expression):
+    """A seed-42 hash of one or more operands, chained column by column. A
+    NULL operand leaves the running hash as it is, so the result is never
+    NULL."""
+
+    fn = ""
+
+    def __init__(self, *exprs):
+        if not exprs:
+            raise ValueError(f"{self.fn} takes at least one argument")
+        self.exprs = [_as_expr(e) for e in exprs]
+
+    @property
+    def children(self):
+        return tuple(self.exprs)
+
+    def _check(self, schema: Schema):
+        for e in self.exprs:
+            dt = e.dtype(schema)
+            if dt.id not in _ROW_HASH_TYPES:
+                raise TypeError(f"{self.fn} over {dt} operands is not "
+                                "supported")
+
+    def nullable(self, schema: Schema) -> bool:
+        return False
+
+    def __str__(self):
+        return f"{self.fn}(" + ", ".join(str(e) for e in self.exprs) + ")"
+
+
+class Murmur3Hash(_RowHash):
+    """hash(e1, ..., ek): Spark's murmur3_x86_32 row hash, INT32
+    (GpuMurmur3Hash analogue)."""
+
+    fn = "hash"
+
+    def dtype(self, schema: Schema) -> DType:
+        self._check(schema)
+        return INT32
+
+    def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
+        self._check(schema)
+        return ops.murmur3_hash([e.eval(batch, schema) for e in self.exprs],
+                                42)
+
+
+class XxHash64(_RowHash):
+    """xxhash64(e1, ..., ek): canonical XXH64 row hash, INT64 (GpuXxHash64
+    analogue)."""
+
+    fn = "xxhash64"
+
+    def dtype(self, schema: Schema) -> DType:
+        self._check(schema)
+        return INT64
+
+    def eval(self, batch: ColumnBatch, schema: Schema) -> Column:
+        self._check(schema)
+        return ops.xxhash64([e.eval(batch, schema) for e in self.exprs], 42)
+
+
 _lambda_ids = itertools.count()
 
 
@@ -1749,6 +1909,31 @@ def sequence(start, stop, step=None) -> Sequence:
 def array_join(a, delimiter: str,
                null_replacement: Optional[str] = None) -> ArrayJoin:
     return _as_expr(a).array_join(delimiter, null_replacement)
+
+
+def md5(e) -> Md5:
+    return Md5(e)
+
+
+def sha1(e) -> Sha1:
+    return Sha1(e)
+
+
+def sha2(e, bits: int) -> Sha2:
+    return Sha2(e, bits)
+
+
+def crc32(e) -> Crc32:
+    return Crc32(e)
+
+
+def hash_(*exprs) -> Murmur3Hash:
+    """hash(e1, ..., ek); the underscore keeps python's hash."""
+    return Murmur3Hash(*exprs)
+
+
+def xxhash64(*exprs) -> XxHash64:
+    return XxHash64(*exprs)
 
 
 class HostStringFn(Expression):

@@ -324,6 +324,26 @@ def murmur3_hash(cols: Sequence[Column], seed: int = 42) -> Column:
     return backend_for(*cols).murmur3_hash(list(cols), seed)
 
 
+def xxhash64(cols: Sequence[Column], seed: int = 42) -> Column:
+    """Canonical XXH64 row hash over the columns, seeds chained, INT64
+    (Hash.xxhash64 / GpuXxHash64 analogue)."""
+    return backend_for(*cols).xxhash64(list(cols), seed)
+
+
+def digest_hex(col: Column, algo: str) -> Column:
+    """md5 / sha1 / sha224 / sha256 / sha384 / sha512 of a STRING column's
+    UTF-8 bytes as lowercase hex strings of one width; NULL where the input
+    is (GpuMd5, GpuSha1, GpuSha2 analogue)."""
+    return backend_for(col).digest_hex(col, algo)
+
+
+def crc32(col: Column) -> Column:
+    """crc32 (zlib polynomial) of a STRING column's UTF-8 bytes as the
+    unsigned value in INT64; NULL where the input is (GpuCrc32
+    analogue)."""
+    return backend_for(col).crc32(col)
+
+
 def hash_partition(batch: ColumnBatch, key_idx: Sequence[int], num_parts: int) -> Tuple[ColumnBatch, List[int]]:
     """Reorder rows so rows of one partition are contiguous; returns the
     reordered batch plus partition start offsets (len num_parts+1)."""

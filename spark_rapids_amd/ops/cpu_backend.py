@@ -2078,6 +2078,35 @@ def xxhash64(cols, seed: int = 42) -> Column:
     return _make(h, None, DType.int64())
 
 
+_DIGESTS = ("md5", "sha1", "sha224", "sha256", "sha384", "sha512")
+
+
+def digest_hex(col: Column, algo: str) -> Column:
+    """hashlib's digest of each row's UTF-8 bytes as lowercase hex; null
+    rows stay null."""
+    import hashlib
+
+    if algo not in _DIGESTS:
+        raise KeyError(algo)
+    if col.dtype.id is not TypeId.STRING:
+        raise TypeError(f"{algo} needs a string input, got {col.dtype}")
+    return Column.from_pylist(
+        [None if v is None
+         else hashlib.new(algo, v.encode("utf-8")).hexdigest()
+         for v in col.to_pylist()], DType.string())
+
+
+def crc32(col: Column) -> Column:
+    """zlib.crc32 of each row's UTF-8 bytes (unsigned) as INT64."""
+    import zlib
+
+    if col.dtype.id is not TypeId.STRING:
+        raise TypeError(f"crc32 needs a string input, got {col.dtype}")
+    return Column.from_pylist(
+        [None if v is None else zlib.crc32(v.encode("utf-8")) & 0xFFFFFFFF
+         for v in col.to_pylist()], DType.int64())
+
+
 def _hll_estimate_host(regs_np) -> np.ndarray:
     """Standard HLL estimate with the small-range linear-counting
     correction (no empirical bias tables — estimates differ slightly from

@@ -3498,6 +3498,49 @@ def xxhash64(cols: List[Column], seed: int = 42) -> Column:
     return Column(DType.int64(), cols[0].size, t, None, null_count=0)
 
 
+# algo id of hipdf_digest_hex and the hex digits of a result
+_DIGEST = {"md5": (0, 32), "sha1": (1, 40), "sha224": (2, 56),
+           "sha256": (3, 64), "sha384": (4, 96), "sha512": (5, 128)}
+
+
+def _need_string(fn: str, col: Column):
+    if col.dtype.id is not TypeId.STRING:
+        raise TypeError(f"{fn} needs a string input, got {col.dtype}")
+
+
+def digest_hex(col: Column, algo: str) -> Column:
+    """md5 / sha1 / sha2 of each row's UTF-8 bytes as lowercase hex: one
+    launch, thread per row. Every result has the same width W, so the
+    offsets are arange * W and nothing is sized or scanned."""
+    _need_string(algo, col)
+    aid, width = _DIGEST[algo]
+    n = col.size
+    if n == 0:
+        return _empty_col(DType.string())
+    if n * width > 2 ** 31 - 1:
+        raise OverflowError(f"{algo} result exceeds int32 offsets")
+    v = col.validity.clone() if col.validity is not None else None
+    out = torch.empty(n * width, **_NO_DATA)
+    ext.digest_hex(aid, col.offsets.data_ptr(), col.data.data_ptr(),
+                   _ptr(col.validity), out.data_ptr(), n, _stream())
+    offs = torch.arange(0, (n + 1) * width, width, dtype=torch.int32,
+                        device="cuda")
+    return Column(DType.string(), n, out, v, offs, col._null_count)
+
+
+def crc32(col: Column) -> Column:
+    """zlib crc32 of each row's UTF-8 bytes, unsigned, as INT64."""
+    _need_string("crc32", col)
+    n = col.size
+    if n == 0:
+        return _empty_col(DType.int64())
+    v = col.validity.clone() if col.validity is not None else None
+    out = torch.empty(n, dtype=torch.int64, device="cuda")
+    ext.crc32_str(col.offsets.data_ptr(), col.data.data_ptr(),
+                  _ptr(col.validity), out.data_ptr(), n, _stream())
+    return Column(DType.int64(), n, out, v, None, col._null_count)
+
+
 def _gb_hll(vc: Column, row_gid: torch.Tensor, selp, n: int, ngroups: int,
             p: int, s) -> Column:
     import numpy as np

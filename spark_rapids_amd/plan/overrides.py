@@ -77,6 +77,7 @@ _ARRAY_SEARCH_FNS = {"ArrayPosition": "array_position",
 _ARRAY_BUILD_FNS = {"CreateArray": "array", "ArrayConcat": "concat",
                     "Flatten": "flatten", "Sequence": "sequence",
                     "ArrayJoin": "array_join"}
+_DIGEST_FNS = ("Md5", "Sha1", "Sha2", "Crc32", "Murmur3Hash", "XxHash64")
 _ARRAY_LAMBDAS = ("ArrayTransform", "ArrayFilter", "ArrayExists",
                   "ArrayForAll")
 
@@ -207,6 +208,8 @@ class Tagger:
             self._tag_array_search(e, schema, out)
         elif type(e).__name__ in _ARRAY_BUILD_FNS:
             self._tag_array_build(e, schema, out)
+        elif type(e).__name__ in _DIGEST_FNS:
+            self._tag_digest(e, schema, out)
         elif type(e).__name__ == "LambdaVariable":
             pass
         elif type(e).__name__ in _ARRAY_LAMBDAS:
@@ -286,6 +289,15 @@ class Tagger:
         if name in ("CreateArray", "ArrayConcat", "Flatten") and \
                 rt.children[0].is_nested:
             out.append(f"{fn} over nested elements on CPU")
+
+    def _tag_digest(self, e, schema, out: List[str]):
+        """md5 / sha1 / sha2 / crc32 hash a string's bytes (digest.hip);
+        hash / xxhash64 take what the murmur3 and xxhash64 kernels take.
+        dtype() checks the operand types and raises for any other."""
+        name = type(e).__name__
+        if not self.conf.expr_enabled(name):
+            out.append(f"expression {name} disabled by conf")
+        e.dtype(schema)
 
     def _tag_array_lambda(self, e, schema, out: List[str]):
         """transform / filter / exists / forall: the body runs as ordinary

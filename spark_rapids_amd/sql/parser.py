@@ -937,6 +937,27 @@ class Parser:
             if len(args) not in (2, 3):
                 raise ValueError("array_join takes two or three arguments")
             return _ex.ArrayJoin(args[0], *args[1:])
+        if name in ("md5", "sha1", "sha", "crc32"):
+            from ..expr import expressions as _ex
+
+            if len(args) != 1:
+                raise ValueError(f"{name} takes one argument")
+            cls = {"md5": _ex.Md5, "sha1": _ex.Sha1, "sha": _ex.Sha1,
+                   "crc32": _ex.Crc32}[name]
+            return cls(args[0])
+        if name == "sha2":
+            from ..expr.expressions import Sha2
+
+            if len(args) != 2:
+                raise ValueError("sha2 takes two arguments")
+            return Sha2(args[0], self._int_operand(args[1]))
+        if name in ("hash", "xxhash64"):
+            from ..expr import expressions as _ex
+
+            if not args:
+                raise ValueError(f"{name} takes at least one argument")
+            return (_ex.Murmur3Hash if name == "hash"
+                    else _ex.XxHash64)(*args)
         if name in ("map_keys", "map_values", "map_entries"):
             from ..expr.expressions import MapView
 

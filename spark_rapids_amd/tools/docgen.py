@@ -128,7 +128,19 @@ _EXPR_ROWS = [
      "GPU*", "top-level fields as columns `c0, c1, ...`; each name is a "
      "literal key, never a path; SQL `json_tuple(j, 'a', 'b') [AS (x, y)]` "
      "in a select list, no `LATERAL VIEW`; otherwise as GetJsonObject"),
-    ("Murmur3Hash", "k_murmur3", "GPU", "spark-exact, seeds chain"),
+    ("Murmur3Hash", "k_murmur3", "GPU",
+     "spark-exact, seeds chain; SQL `hash(a, b, ...)`, API `hash_(...)`, "
+     "seed 42, INT32, never NULL; fixed-width (<= 64 bit) and string "
+     "operands"),
+    ("Md5", "md5(s)", "GPU",
+     "thread-per-row digest kernel (digest.hip), lowercase hex; STRING "
+     "input, its UTF-8 bytes are hashed"),
+    ("Sha1", "sha1(s) / sha(s)", "GPU", "as Md5, 40 hex digits"),
+    ("Sha2", "sha2(s, bits)", "GPU",
+     "SHA-224/256/384/512; bits an int literal, 0 means 256, any other "
+     "value gives NULL"),
+    ("Crc32", "crc32(s)", "GPU",
+     "zlib polynomial, table staged in LDS; unsigned value as BIGINT"),
     # datetime
     ("Year", "UnaryExpr year", "GPU", "civil calendar kernel"),
     ("Month", "UnaryExpr month", "GPU", ""),
@@ -165,7 +177,9 @@ _EXPR_ROWS = [
     ("Percentile", "gb_percentile", "GPU", "exact sorted-groups kernel"),
     ("ApproximatePercentile", "exact rewrite", "GPU", "exact result (superset of t-digest accuracy)"),
     ("ApproxCountDistinct/HyperLogLogPlusPlus", "k_gb_hll + xxHash64", "GPU", "HLL++ sketch, Spark precision formula; estimates use standard HLL correction (no bias tables)"),
-    ("XxHash64", "k_xxhash64_col/str", "GPU", "canonical XXH64, column-chained seeds"),
+    ("XxHash64", "k_xxhash64_col/str", "GPU",
+     "canonical XXH64, column-chained seeds; SQL / API `xxhash64(a, b, "
+     "...)`, seed 42, INT64, never NULL"),
     ("BitAndAgg/BitOrAgg/BitXorAgg", "bit_and/or/xor", "GPU", ""),
     ("PivotFirst", "-", "CPU", "via host fallback"),
     # windows
